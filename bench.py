@@ -13,13 +13,15 @@ every rank runs its own B=32 batch and the flat gradient buffers are mean-all-re
 
 Default arithmetic = BASELINE.json's GPU configuration ("Yahoo LSTM-VAE bf16"): the large GEMMs run on the bf16 matrix
 pipe with f32 accumulate, f32 master weights / activations / gradients, f32 LSTM recurrence; `--dtype f32` times the
-exact-f32 parity path (the one the 1e-4 ELBO parity tests run), and the default line carries that number too
+exact-f32 parity path (the one the 1e-4 ELBO parity tests run), and the `--full` line carries that number too
 (`f32_parity_path`).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (the kernel group with the largest
-share of the step, bracketed live by HIP events on its launch stream inside the timed region; the other group is
-`roofline_secondary`) and `cpu_baseline` (the CPU oracle's ATen path = the reference's CPU op sequence, timed on this
-box's host cores on a bounded sample).
+Prints ONE JSON line (rank 0) with the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step =
+milliseconds per timed step).  A plain run sets up, warms up, times --steps steps (no HIP events inside them), writes
+--dump-outputs and prints the line; `--full` adds what takes passes or processes of its own: `roofline` (the kernel group
+with the largest share of the step, bracketed live by HIP events on its launch stream inside the timed region; the other
+group is `roofline_secondary`), the side runs and `cpu_baseline` (the CPU oracle's ATen path = the reference's CPU op
+sequence, timed on this box's host cores on a bounded sample).
 """
 import argparse
 import json
@@ -90,6 +92,42 @@ def emit(out):
         open(os.environ["LVAE_BENCH_DONE"], "w").write("done\n")
 
 
+DUMP_SAMPLE = 1 << 18             # --dump-outputs: elements kept of a larger tensor (the Yahoo dump is ~15 MB in all)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, vae, tr, stats, decoder_grads=True):
+    """--dump-outputs: what the timed path handed its caller after its LAST step, as <path>/<name>.npy -- every parameter
+    (`param.<name>`: the encoder's as the update left it), every .grad (`grad.<name>`; decoder_grads=False: the encoder's only,
+    the decoder's are unspecified under --decoder-grads norm), the step's per-sequence `loss` / `rec` / `kl` (text trainer) in
+    float32, and `stats` in float64 = [loss_sum, rec_sum, kl_sum] over the timed steps + the last step's [grad norm, clip coef].
+    A tensor of more than DUMP_SAMPLE elements is written as a fixed sample of its flattened elements (seeded by its name, so
+    the same positions in every run).  Two builds run with the same arguments see the same inputs and can be compared array by array."""
+    import zlib
+    arrays = {"stats": np.array([stats[k] for k in ("loss_sum", "rec_sum", "kl_sum", "norm", "coef")], dtype=np.float64)}
+    static = getattr(tr, "static", None)
+    if static and getattr(tr, "micro_batches", 1) == 1:
+        st = next(reversed(static.values()))                # the per-shape buffers of the last step (trainer._static_for)
+        for k in ("loss", "rec", "kl"):
+            arrays[k] = getattr(st, k)
+    for name, p in vae.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None and (decoder_grads or not name.startswith("decoder.")):
+            arrays["grad." + name] = p.grad
+    for name, t in arrays.items():
+        if torch.is_tensor(t):
+            t = t.detach()
+            if t.numel() > DUMP_SAMPLE:
+                idx = np.unique(np.random.RandomState(zlib.crc32(name.encode())).randint(0, t.numel(), DUMP_SAMPLE))
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "dump of %d bytes > %d" % (total, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def measure_omniglot(args, dev, rank, world, cpu_baseline=False, profile_eager=False):
     """images/sec through the aggressive inner step of the Omniglot VAE (image.py:300-314), B=50 per GPU, replicas only
     (BatchNorm batch statistics make naive data parallelism non-equivalent: SURVEY.md 8e).  profile_eager: take the per-group
@@ -121,7 +159,9 @@ def measure_omniglot(args, dev, rank, world, cpu_baseline=False, profile_eager=F
     prof = {}
     prof_steps = 0
     stats = tr.read_stats()
-    if not args.graph or profile_eager:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vae, tr, stats)
+    if args.full and (not args.graph or profile_eager):
         if args.graph:
             tr = AggressiveImageTrainer(vae, lr=1e-3, clip=5.0, seed=783435 + rank, precision=args.dtype, use_graph=False)
             one_step()                                      # allocate the eager path's buffers outside the profiled steps
@@ -192,7 +232,7 @@ def measure_omniglot(args, dev, rank, world, cpu_baseline=False, profile_eager=F
                                    "a device-side sleep), the eager step itself is host-launch bound and the hipGraph replay is not")
     else:
         out["roofline"] = {"bound": "mfma", "achieved": None, "peak": peak, "unit": "TFLOP/s", "frac": None, "traffic": None,
-                           "note": "graph replay: no per-kernel events; see the eager run / profiles/ for the kernel breakdown"}
+                           "note": "no per-kernel events (graph replay, or a run without --full); see the eager run with --full / profiles/ for the kernel breakdown"}
     if cpu_baseline:
         from oracle import image_vae_oracle as IO          # the checker, used here only as the timed CPU baseline
         nthreads = min(32, os.cpu_count() or 1)
@@ -745,9 +785,18 @@ def main():
     ap.add_argument("--tokens", default="uniform", choices=["uniform", "zipf"],
                     help="distribution of the synthetic token ids: uniform (SURVEY.md 8d, the default) or Zipf-like (natural text: frequent "
                          "tokens repeat hundreds of times per batch, which the embedding backward's sort / scatter feel)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the kernel groups bracketed by HIP events (roofline), the 200-step and "
+                         "cold-batch passes, the other arithmetics and BASELINE.json configurations (side runs), the drop-in path, the CPU "
+                         "baseline with the ELBO check and the PyTorch-ROCm yardstick (--no-* switch single legs off).  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.vendor_leg:
         return vendor_leg_main(args.vendor_leg, args.vendor_autocast)
+    if not args.full:
+        args.no_side_runs = args.no_cpu_baseline = args.no_vendor_baseline = True
     if os.environ.get("LVAE_BENCH_WATCHDOG"):
         # diagnostics: dump every thread's Python stack to stderr after this many seconds (and again every period) without exiting
         import faulthandler
@@ -884,7 +933,7 @@ def main():
         tr.commit()
     if dp:
         torch.distributed.barrier()
-    if not args.graph and not emu:
+    if args.full and not args.graph and not emu:
         # the dominant kernel group (the four LSTM recurrences) is bracketed live inside the timed region; the GEMM group's events
         # (22 records per step, ~5 us of queue idle each) are taken in a separate untimed pass right after it
         prof = {}
@@ -903,6 +952,8 @@ def main():
     engine.PROFILE = None
     engine.PROFILE_PREFIX = None
     stats_timed = tr.read_stats()                            # report sums of the timed region alone (the passes below add steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vae, tr, stats_timed, decoder_grads=args.decoder_grads == "full")
     prof_gemm, gemm_steps = None, 0
     if prof is not None:
         prof_gemm, gemm_steps = {}, min(args.steps, 5 if not stress else 3)
@@ -1090,7 +1141,7 @@ def main():
         out["roofline"] = {"bound": "mfma", "achieved": round(step_flops / step_s / 1e12, 2),
                            "peak": peak_mfma, "unit": "TFLOP/s",
                            "frac": round(step_flops / step_s / 1e12 / peak_mfma, 4),
-                           "traffic": None, "note": "whole-step algorithmic flops (graph replay: no per-kernel events)"}
+                           "traffic": None, "note": "whole-step algorithmic flops (no per-kernel events: graph replay, or a run without --full)"}
 
     if world == 1 and args.dtype == "bf16" and args.encoder_forward == "bf16" and not args.graph and not stress and not args.no_side_runs:
         # the bf16 configuration with the encoder's forward in exact f32 (ELBO, rec AND KL within 1e-4 of the reference CPU path:
@@ -1144,7 +1195,7 @@ def main():
             # squares in their producers, never written: an option, not the headline -- .grad of those two tensors is then unspecified)
             side["yahoo_decoder_grads_norm"] = side_run_text("yahoo", dev, steps=20, warmup=3, decoder_grads="norm")
             oa = argparse.Namespace(**vars(args))
-            oa.graph, oa.dtype, oa.steps, oa.warmup, oa.pool = 1, "f32", 20, 5, 16
+            oa.graph, oa.dtype, oa.steps, oa.warmup, oa.pool, oa.dump_outputs = 1, "f32", 20, 5, 16, None
             om = measure_omniglot(oa, dev, 0, 1, cpu_baseline=False, profile_eager=True)
             side["omniglot"] = {"value": om["value"], "unit": om["unit"], "ms_per_step": om["ms_per_step"], "dtype": om["dtype"],
                                 "steps": om["steps"], "workload": om["config"]["workload"] + ", hipGraph replay",

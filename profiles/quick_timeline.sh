@@ -4,5 +4,5 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_q
-rocprofv3 --kernel-trace -d /tmp/prof_q -o q -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-side-runs "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace -d /tmp/prof_q -o q -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-side-runs "$@" > /dev/null 2>&1
 python $R/profiles/timeline_rocpd.py /tmp/prof_q/q_results.db 8

@@ -4,6 +4,7 @@ Produces tests/emu/liblvae_emu.so exposing the same C ABI as liblvae_hip.so but 
 pointers.  Used only by `-m "not gpu"` tests to check kernel index math and host launch sequencing
 on the GPU-less CI box.  The package never loads this library (see vae_lagging_encoder_amd/_lib.py).
 """
+import fcntl
 import hashlib
 import os
 import subprocess
@@ -28,6 +29,16 @@ def _digest():
 
 
 def build_emu(force=False):
+    # the ranks of a multi-rank emulator run (bench.py --gpus N under LVAE_BENCH_EMU) all call this at once on a fresh tree:
+    # one builds, the others wait and find it built; the library is linked under a temporary name and renamed into place, so
+    # that no process ever opens a half-written one
+    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
+    with open(os.path.join(HERE, "build", ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        return _build_locked(force)
+
+
+def _build_locked(force):
     dg = _digest()
     if not force and os.path.exists(LIB) and os.path.exists(STAMP):
         with open(STAMP) as fh:
@@ -36,7 +47,6 @@ def build_emu(force=False):
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
     objs = []
     procs = []
-    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for s in srcs:
         o = os.path.join(HERE, "build", os.path.basename(s) + ".o")
         objs.append(o)
@@ -48,11 +58,13 @@ def build_emu(force=False):
         if p.returncode != 0:
             raise RuntimeError("g++ (emu) failed on %s:\n%s" % (s, out))
     impl = os.path.join(HERE, "hip_emu_impl.cpp")
+    tmp = os.path.join(HERE, "build", os.path.basename(LIB))
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-pthread", "-DLV_EMU", "-I", HERE,
-           impl] + objs + ["-o", LIB]
+           impl] + objs + ["-o", tmp]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("g++ (emu link) failed:\n" + res.stdout + res.stderr)
+    os.replace(tmp, LIB)
     with open(STAMP, "w") as fh:
         fh.write(dg)
     return LIB
