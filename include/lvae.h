@@ -400,6 +400,22 @@ int lv_calc_mi_f32(const float* mu, const float* logvar, const float* z, float* 
  * sum_b (mu[b][k] - mean[k])^2 */
 int lv_au_accum_f32(const float* mu, const float* mean, float* acc_dev, int B, int nz, void* stream);
 
+/* ---- model posterior on a latent grid (lv_grid_posterior.hip): VAE.eval_log_model_posterior / calc_model_posterior_mean
+ * (modules/vae.py:170-196, 256-273), the synthetic experiment's plots (toy.py:188-231, 391-462, 482-483).
+ * lv_dec_cond_ll_f32: log p(x_b | z_{b,s}) of LSTMDecoder.log_probability (dec_lstm.py:66-148, 156-161) in eval mode (no
+ * dropout) for x [B][T] and K samples per sentence at z + b*z_stride ([K][nz]; z_stride = 0: one grid shared by every
+ * sentence) -> cond_ll [B][K]; weights as the module stores them; ws: lv_dec_cond_ll_f32_ws_floats floats, 16-byte aligned.
+ * lv_dec_cond_ll_f32_supported: 1 inside the kernel's envelope (H <= 128, nz <= 64, T >= 2), else 0 (-4 from the call). */
+int lv_dec_cond_ll_f32_supported(int V, int ni, int H, int nz, int T);
+long lv_dec_cond_ll_f32_ws_floats(int V, int H, int nz, int B, int T);
+int lv_dec_cond_ll_f32(const int64_t* x, int B, int T, const float* z, long z_stride, int K, const float* embed,
+                       const float* trans, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       const float* pred, int V, int ni, int H, int nz, float* ws, float* cond_ll, void* stream);
+/* the grid normalisation: joint = log N(z; 0, I) + cond_ll, log_post = joint - log_sum_exp_k(joint) (log_post may be NULL),
+ * mean [B][nz] = sum_k exp(log_post_k) z_k */
+int lv_grid_posterior_f32(const float* cond_ll, const float* z, long z_stride, int B, int K, int nz, float* log_post,
+                          float* mean, void* stream);
+
 /* ---- generation helpers (lv_eval.hip; SURVEY.md 8f row 4: modules/decoders/dec_lstm.py:163-367) -------------------------
  * torch.argmax(logits, dim=1) (greedy_decode, dec_lstm.py:304): lowest index among equal maxima */
 int lv_argmax_rows_f32(const float* in, long ld, int R, int C, int64_t* idx, void* stream);

@@ -162,11 +162,15 @@ SIGNATURES = {
     "lv_sigmoid_bce_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "lv_dec_input_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_dec_input_bwd_f32": [_vp, _vp, _i, _i, _i, _vp],
+    "lv_dec_cond_ll_f32_supported": [_i, _i, _i, _i, _i],
+    "lv_dec_cond_ll_f32_ws_floats": [_i, _i, _i, _i, _i],
+    "lv_dec_cond_ll_f32": [_vp, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "lv_grid_posterior_f32": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp],
 }
 
 
 _LONG_FNS = ("lv_lstm_ws_floats", "lv_conv1x1_wgrad_ws_floats", "lv_conv1x1_blocks", "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats", "lv_conv32_wpack_floats",
-             "lv_conv32_wgrad_ws_floats")
+             "lv_conv32_wgrad_ws_floats", "lv_dec_cond_ll_f32_ws_floats")
 
 
 class LvaeError(RuntimeError):
@@ -195,7 +199,8 @@ class Lib(object):
         self._value_fns = {"lv_gemm_b16_dual_supported", "lv_gemm_b16_pair_supported", "lv_lstm_bwd_ksplit", "lv_dec_tail_parts", "lv_gemm_b16_nll_parts", "lv_gemm_b16_sumsq_parts", "lv_embed_scatter_sumsq_parts", "lv_conv32_wpack_floats",
                            "lv_conv32_wgrad_slabs", "lv_conv32_wgrad_ws_floats", "lv_conv32_wgrad_parts", "lv_conv1x1_wgrad_parts", "lv_conv32_blocks", "lv_conv1x1_blocks", "lv_conv1x1_wgrad_ws_floats", "lv_sumsq_workspace_floats", "lv_lstm_ws_floats", "lv_bn_workspace_floats",
                            "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats",
-                           "lv_pixelcnn_net_words", "lv_pixelcnn_block_words", "lv_conv32_tap_split"}
+                           "lv_pixelcnn_net_words", "lv_pixelcnn_block_words", "lv_conv32_tap_split", "lv_dec_cond_ll_f32_supported",
+                           "lv_dec_cond_ll_f32_ws_floats"}
 
     def __getattr__(self, name):
         if name.startswith("lv_"):

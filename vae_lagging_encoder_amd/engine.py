@@ -1387,6 +1387,38 @@ class LSTMDecoderEngine(object):
         self.last = (x, z2, mask_in, mask_out, sc_in, sc_out, B, T, self.gen)
         return w.rec
 
+    def cond_ll_supported(self, T):
+        """True where lv_dec_cond_ll_f32 takes this decoder's shape with T-token sentences (H <= 128, nz <= 64)."""
+        V, ni, H, nz = self.dims()
+        return bool(self.lib.lv_dec_cond_ll_f32_supported(V, ni, H, nz, int(T)))
+
+    def cond_ll(self, x, z):
+        """log p(x|z) of the eval-mode decoder (no dropout) through lv_dec_cond_ll_f32: x int64 [B][T]; z [K][nz] (one grid
+        shared by every sentence, never expanded) or [B][K][nz] -> [B][K].  The caller checks cond_ll_supported().  Not
+        differentiable.  Every operand must live on x's device: the kernels take raw pointers, so a mismatch is refused here,
+        before anything is launched."""
+        device = x.device
+        if z.device != device:
+            raise _lib.LvaeError("cond_ll: z is on %s, x on %s" % (z.device, device))
+        self.ensure(device)
+        V, ni, H, nz = self.dims()
+        v = self.flat.views
+        B, T = x.shape
+        if x.dtype != torch.int64 or z.dim() not in (2, 3) or z.shape[-1] != nz or (z.dim() == 3 and z.shape[0] != B):
+            raise ValueError("cond_ll: x int64 [B][T] and z [K][%d] or [B][K][%d] expected, got %s %s and %s"
+                             % (nz, nz, x.dtype, tuple(x.shape), tuple(z.shape)))
+        x = x.contiguous()
+        z = z.contiguous().float()
+        K = z.shape[-2]
+        z_stride = 0 if z.dim() == 2 else K * nz
+        ws = torch.empty(self.lib.lv_dec_cond_ll_f32_ws_floats(V, H, nz, B, T), dtype=torch.float32, device=device)
+        out = torch.empty(B, K, dtype=torch.float32, device=device)
+        self.lib.lv_dec_cond_ll_f32(P(x), B, T, P(z), z_stride, K, P(v["embed.weight"]), P(v["trans_linear.weight"]),
+                                    P(v["lstm.weight_ih_l0"]), P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]),
+                                    P(v["lstm.bias_hh_l0"]), P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), P(out),
+                                    stream_ptr(device))
+        return out
+
     def backward(self, drec, gen=None, partial_dz=False):
         """drec [B] = dL/d rec_b -> fills self.flat.grad; returns dz [B][nz] (partial_dz: the tail kernel's partial sums
         [parts][B][nz] and their count instead)."""
@@ -1535,6 +1567,23 @@ def logsumexp_rows(x, add=0.0):
     out = torch.empty(R, dtype=torch.float32, device=x.device)
     lib.lv_logsumexp_rows_f32(P(x), C, R, C, float(add), P(out), s)
     return out
+
+
+def grid_posterior(cond_ll, z, want_log_post=True):
+    """Normalisation of log p(x|z) over a latent grid (VAE.eval_log_model_posterior / calc_model_posterior_mean): cond_ll [B][K],
+    z [K][nz] (shared grid) or [B][K][nz] -> (log p(z|x) [B][K] or None, E[z|x] [B][nz])."""
+    if z.device != cond_ll.device:
+        raise _lib.LvaeError("grid_posterior: z is on %s, cond_ll on %s" % (z.device, cond_ll.device))
+    lib, s = backend_for(cond_ll.device), stream_ptr(cond_ll.device)
+    cond_ll, z = cond_ll.contiguous().float(), z.contiguous().float()
+    B, K = cond_ll.shape
+    nz = z.shape[-1]
+    if z.dim() not in (2, 3) or z.shape[-2] != K or (z.dim() == 3 and z.shape[0] != B):
+        raise ValueError("grid_posterior: z [%d][nz] or [%d][%d][nz] expected, got %s" % (K, B, K, tuple(z.shape)))
+    log_post = torch.empty(B, K, dtype=torch.float32, device=cond_ll.device) if want_log_post else None
+    mean = torch.empty(B, nz, dtype=torch.float32, device=cond_ll.device)
+    lib.lv_grid_posterior_f32(P(cond_ll), P(z), 0 if z.dim() == 2 else K * nz, B, K, nz, P(log_post), P(mean), s)
+    return log_post, mean
 
 
 def calc_mi(mu, logvar, z):

@@ -9,6 +9,7 @@ import math
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from .. import engine as _eng
 from .utils import log_sum_exp
 
@@ -142,13 +143,49 @@ class VAE(nn.Module):
     def eval_inference_dist(self, x, z, param=None):
         return self.encoder.eval_inference_dist(x, z, param)
 
+    # True: eval_log_model_posterior / calc_model_posterior_mean take lv_grid_posterior.hip where _fused_grid_ok allows it;
+    # False forces the generic route below (A/B runs, tests)
+    fused_grid = True
+
+    def _fused_grid_ok(self, x, grid_z):
+        """The fused grid kernels compute the eval-mode decoder without autograd: usable when no dropout mask would be drawn
+        (the decoder is not training, or both its dropout p are 0), autograd is off (every call site in toy.py runs under
+        torch.no_grad(); with grad enabled the generic route keeps the result differentiable), x and the grid share one
+        device, and an LSTM decoder is inside lv_dec_cond_ll_f32's envelope on a device the package has kernels for.
+        Anything else keeps the generic route and its behaviour, errors included (e.g. toy.py's epoch-end dump, which runs in
+        train mode and draws dropout masks there)."""
+        dec = self.decoder
+        eng = getattr(dec, "_hip", None)
+        if not (self.fused_grid and not torch.is_grad_enabled() and isinstance(eng, _eng.LSTMDecoderEngine)
+                and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.int64 and torch.is_tensor(grid_z)
+                and grid_z.device == x.device and grid_z.dim() == 2 and grid_z.size(1) == self.nz):
+            return False
+        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
+            return False
+        try:
+            eng.ensure(x.device)
+        except _lib.LvaeError:
+            return False
+        return eng.cond_ll_supported(x.size(1))
+
+    def _fused_grid_posterior(self, x, grid_z, want_log_post):
+        cond = self.decoder._hip.cond_ll(x, grid_z)
+        return _eng.grid_posterior(cond, grid_z, want_log_post)
+
     def eval_log_model_posterior(self, x, grid_z):
-        """log p(z|x) on a grid of K points (K, nz) -> (batch, K), normalised over the grid."""
+        """log p(z|x) on a grid of K points (K, nz) -> (batch, K), normalised over the grid.  Eval-mode LSTM decoder inside the
+        envelope, under torch.no_grad(): one lv_dec_cond_ll_f32 + one lv_grid_posterior_f32 launch (the grid is shared, never
+        expanded; no logits)."""
+        if self._fused_grid_ok(x, grid_z):
+            return self._fused_grid_posterior(x, grid_z, True)[0]
         n = x.size(0) if torch.is_tensor(x) else x[0].size(0)
         joint = self.eval_complete_ll(x, grid_z.unsqueeze(0).expand(n, *grid_z.size()).contiguous())
         return joint - log_sum_exp(joint, dim=1, keepdim=True)
 
     def calc_model_posterior_mean(self, x, grid_z):
+        """E[z|x] over the grid (K, nz) -> (batch, nz); the fused route as eval_log_model_posterior's."""
+        if self._fused_grid_ok(x, grid_z):
+            return self._fused_grid_posterior(x, grid_z, False)[1]
         w = self.eval_log_model_posterior(x, grid_z).exp()
         return (w.unsqueeze(2) * grid_z.unsqueeze(0)).sum(1)
 
