@@ -372,6 +372,17 @@ int lv_sgd_step_scale_txn_f32(float* p, float* g, long n, const float* lr_dev, c
                               float* x2, long n2, const float* void_flag_dev, void* stream);
 int lv_adam_step_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev,
                      const float* step_dev, float beta1, float beta2, float eps, int write_back_clipped, void* stream);
+/* lv_adam_step_f32 behind the transaction gate (the fused text trainer's optimizer="adam"): torch.optim.Adam (amsgrad=False,
+ * weight_decay=0) on the clipped gradient, with bias corrections for step number step_dev[0] + 1; a one-thread launch queued behind the
+ * update then advances step_dev[0] (the optimizer's committed-step count, one per optimizer).  While void_flag_dev[0] != 0, p, g, m, v
+ * and step_dev stay bit-unchanged.  The betas are doubles, as torch's Python floats are: 1 - beta and the bias corrections are formed
+ * in double and rounded to f32 where they meet the tensors, as torch rounds them. */
+int lv_adam_step_txn_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev, float* step_dev,
+                         double beta1, double beta2, float eps, int write_back_clipped, const float* void_flag_dev, void* stream);
+/* lv_adam_step_txn_f32 on (p, g, m, v) and lv_scale_txn_f32 on x2, the gradient of the side that is NOT stepped, in one launch */
+int lv_adam_step_scale_txn_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev,
+                               float* step_dev, double beta1, double beta2, float eps, int write_back_clipped, float* x2, long n2,
+                               const float* void_flag_dev, void* stream);
 
 /* ---- Philox4x32-10 draws for throughput mode (stand-in for torch's generator at encoder.py:77, dec_lstm.py:81,106)
  * state_dev: uint64[2] = {seed, offset} in device memory */

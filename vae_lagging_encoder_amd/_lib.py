@@ -15,6 +15,7 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _l = ctypes.c_long
 _f = ctypes.c_float
+_d = ctypes.c_double
 _u64 = ctypes.c_uint64
 
 # name -> argtypes (all functions return int status: 0 ok, >0 hipError_t, <0 argument check)
@@ -107,6 +108,8 @@ SIGNATURES = {
     "lv_sgd_step_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp],
     "lv_scale_f32": [_vp, _l, _vp, _vp],
     "lv_adam_step_f32": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _f, _f, _f, _i, _vp],
+    "lv_adam_step_txn_f32": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _d, _d, _f, _i, _vp, _vp],
+    "lv_adam_step_scale_txn_f32": [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _d, _d, _f, _i, _vp, _l, _vp, _vp],
     "lv_add_scalar_f32": [_vp, _f, _vp],
     "lv_sum_accum_f32": [_vp, _l, _vp, _vp],
     "lv_gauss_logpdf_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],

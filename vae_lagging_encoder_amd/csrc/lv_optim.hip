@@ -314,6 +314,85 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     }
 }
 
+// One element of torch.optim.Adam (amsgrad=False, weight_decay=0) on the clipped gradient c * g[i]: the same operation order as
+// torch's _single_tensor_adam -- m.lerp_(g, 1 - beta1), v.mul_(beta2).addcmul_(g, g, 1 - beta2), p.addcdiv_(m, sqrt(v) / bc2s + eps,
+// -step_size)
+__device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v, float c, float w1, float beta2, float w2, float step_size,
+                                          float bc2s, float eps, bool wb) {
+    const float gv = g * c;
+    const float mi = m + w1 * (gv - m);
+    const float vi = v * beta2 + w2 * gv * gv;
+    const float denom = sqrtf(vi) / bc2s + eps;
+    p = p - step_size * (mi / denom);
+    m = mi;
+    v = vi;
+    if (wb) g = gv;
+}
+
+// The gated Adam step of the fused text trainer (lv_adam_step_txn_f32 / lv_adam_step_scale_txn_f32): a no-op while the transaction
+// gate's void flag is up.  step[0] counts the COMMITTED steps of this optimizer; the bias corrections use step[0] + 1, the step
+// number after this one, and adam_tick_kernel, queued behind this launch, advances the counter (no workgroup here writes it).
+// x2 / n2: the gradient buffer of the side that is not stepped, scaled by the clip coefficient in the same launch.
+__global__ __launch_bounds__(256) void adam_txn_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, long n, const float* __restrict__ lr,
+                                                       const float* __restrict__ coef, const float* __restrict__ step,
+                                                       double beta1, double beta2, float eps, int write_back,
+                                                       const float* __restrict__ void_flag, float* __restrict__ x2, long n2) {
+    if (void_flag[0] != 0.f) return;
+    const float c = coef ? coef[0] : 1.f;
+    const long stride = (long)gridDim.x * 256;
+    const long tid0 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (x2 && c != 1.0f) {
+        const long m4 = (((uintptr_t)x2) & 15) == 0 ? n2 / 4 : 0;
+        float4* x4 = reinterpret_cast<float4*>(x2);
+        for (long i = tid0; i < m4; i += stride) {
+            float4 t = x4[i];
+            t.x *= c; t.y *= c; t.z *= c; t.w *= c;
+            x4[i] = t;
+        }
+        for (long i = m4 * 4 + tid0; i < n2; i += stride) x2[i] *= c;
+    }
+    // the betas, 1 - beta and the bias corrections as torch forms them: Python floats (double), rounded to f32 where they meet the
+    // tensors
+    const double t = (double)step[0] + 1.0;
+    const double bc1 = 1.0 - pow(beta1, t);
+    const double bc2 = 1.0 - pow(beta2, t);
+    const float step_size = (float)((double)lr[0] / bc1);
+    const float bc2s = (float)sqrt(bc2);
+    const float w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2), b2 = (float)beta2;
+    const bool wb = write_back && c != 1.0f;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+    const long n4 = vec ? n / 4 : 0;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* m4v = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    for (long i = tid0; i < n4; i += stride) {
+        float4 pv = p4[i], gv = g4[i], mv = m4v[i], vv = v4[i];
+        adam_elem(pv.x, gv.x, mv.x, vv.x, c, w1, b2, w2, step_size, bc2s, eps, wb);
+        adam_elem(pv.y, gv.y, mv.y, vv.y, c, w1, b2, w2, step_size, bc2s, eps, wb);
+        adam_elem(pv.z, gv.z, mv.z, vv.z, c, w1, b2, w2, step_size, bc2s, eps, wb);
+        adam_elem(pv.w, gv.w, mv.w, vv.w, c, w1, b2, w2, step_size, bc2s, eps, wb);
+        p4[i] = pv;
+        m4v[i] = mv;
+        v4[i] = vv;
+        if (wb) g4[i] = gv;
+    }
+    for (long i = n4 * 4 + tid0; i < n; i += stride) {
+        float pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+        adam_elem(pv, gv, mv, vv, c, w1, b2, w2, step_size, bc2s, eps, wb);
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+        if (wb) g[i] = gv;
+    }
+}
+
+// step[0] += 1 unless the step was voided: one thread, queued behind adam_txn_kernel
+__global__ void adam_tick_kernel(float* step, const float* void_flag) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && void_flag[0] == 0.f) step[0] = step[0] + 1.f;
+}
+
 // out[0] += sum(x[0..n))  (single workgroup; n is a batch size)
 __global__ __launch_bounds__(256) void sum_accum_kernel(const float* __restrict__ x, long n, float* out) {
     __shared__ float red[4];
@@ -458,6 +537,35 @@ extern "C" int lv_adam_step_f32(float* p, float* g, float* m, float* v, long n, 
               beta1, beta2, eps, write_back_clipped);
     LV_CHECK_LAUNCH();
     return LV_OK;
+}
+
+// lv_adam_step_f32 behind the transaction gate: p, g, m, v and the step counter step_dev[0] stay untouched while void_flag_dev[0] != 0;
+// otherwise the step is taken with bias corrections for step number step_dev[0] + 1 and the counter advances by one
+static int adam_step_txn(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev, float* step_dev,
+                         double beta1, double beta2, float eps, int write_back_clipped, float* x2, long n2, const float* void_flag_dev,
+                         void* stream) {
+    if (!p || !g || !m || !v || !lr_dev || !step_dev || !void_flag_dev || n < 0 || n2 < 0) return LV_ERR_ARG;
+    LV_LAUNCH(adam_txn_kernel, dim3(lv_stream_grid(n > n2 ? n : n2)), dim3(256), 0, stream, p, g, m, v, n, lr_dev, coef_dev,
+              (const float*)step_dev, beta1, beta2, eps, write_back_clipped, void_flag_dev, x2, n2);
+    LV_LAUNCH(adam_tick_kernel, dim3(1), dim3(64), 0, stream, step_dev, void_flag_dev);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+extern "C" int lv_adam_step_txn_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev,
+                                    float* step_dev, double beta1, double beta2, float eps, int write_back_clipped,
+                                    const float* void_flag_dev, void* stream) {
+    return adam_step_txn(p, g, m, v, n, lr_dev, coef_dev, step_dev, beta1, beta2, eps, write_back_clipped, nullptr, 0, void_flag_dev,
+                         stream);
+}
+
+// lv_adam_step_txn_f32 on (p, g, m, v) + lv_scale_txn_f32 on x2 (the gradient of the side that is not stepped) in one launch
+extern "C" int lv_adam_step_scale_txn_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev,
+                                          float* step_dev, double beta1, double beta2, float eps, int write_back_clipped, float* x2,
+                                          long n2, const float* void_flag_dev, void* stream) {
+    if (!coef_dev || !x2) return LV_ERR_ARG;
+    return adam_step_txn(p, g, m, v, n, lr_dev, coef_dev, step_dev, beta1, beta2, eps, write_back_clipped, x2, n2, void_flag_dev,
+                         stream);
 }
 
 extern "C" int lv_sum_accum_f32(const float* x, long n, float* out_dev, void* stream) {

@@ -67,8 +67,14 @@ class AggressiveTextTrainer(object):
     BUCKET_MIN_ELEMS = 1 << 20
 
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
-                 precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None):
-        """encoder_forward = "f32" (with precision="bf16"): the encoder's FORWARD (input projection + recurrence) with f32-like
+                 precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
+        """optimizer = "sgd" (default: optim.SGD(momentum=0), text.py:325-326) or "adam": torch.optim.Adam(lr, betas, eps) on each of
+        the two sides, as toy.py --optim adam builds them (toy.py:289-290) -- first and second moments per flat buffer, one step
+        count per optimizer in device memory, all behind the transaction gate (lv_adam_step_txn_f32: a voided step moves none of
+        them).  `lr` is the learning rate of either optimizer; reset_optimizer() re-creates them (toy.py:506-511).  Single GPU,
+        one micro-batch.
+        encoder_forward = "f32" (with precision="bf16"): the encoder's FORWARD (input projection + recurrence) with f32-like
         weights inside the bf16 configuration (engine._exact_forward_split: split-bf16 operands + a two-pass recurrence; on a
         fallback rung the exact-f32 kernels).  mu / logvar -- hence z and the KL of encoder.py:55 -- depend on the forward's last
         state alone (enc_lstm.py:60-62), which the WEIGHTS' rounding moves (profiles/r05a_kl_ablation.txt): KL within 2e-5 of the
@@ -88,6 +94,12 @@ class AggressiveTextTrainer(object):
         self.vae = vae
         self.micro_batches = int(micro_batches)
         assert self.micro_batches >= 1
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("optimizer: 'sgd' or 'adam', not %r" % (optimizer,))
+        if optimizer == "adam" and (grad_sync is not None or self.micro_batches > 1):
+            raise ValueError("optimizer='adam' runs on a single GPU with micro_batches = 1 (no grad_sync): the Adam step is not "
+                             "implemented for data parallelism or gradient accumulation")
+        self.optimizer = optimizer
         self.fold_norm = bool(fold_norm)
         assert decoder_grads in ("full", "norm")
         self.decoder_grads = decoder_grads
@@ -134,8 +146,14 @@ class AggressiveTextTrainer(object):
         # device scalars: [0 kl_weight, 1 lr, 2 sumsq, 3 coef, 4 norm, 5 loss_sum, 6 rec_sum, 7 kl_sum,
         #                  8 void flag, 9 steps committed, 10..12 (loss, rec, kl) sums of the step in flight]  -- 8..12 = the
         # transaction block of lv_clip_*_txn_f32: a step whose persistent recurrences timed out is voided on the device
+        # 13, 14: committed-step counts of the encoder's / decoder's Adam (optimizer="adam")
         self.scal = torch.zeros(16, dtype=torch.float32, device=d)
         self.scal[1] = lr
+        self.betas, self.adam_eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.adam_m = self.adam_v = None
+        if optimizer == "adam":
+            self.adam_m = {"enc": torch.zeros_like(self.enc.flat.data), "dec": torch.zeros_like(self.dec.flat.data)}
+            self.adam_v = {"enc": torch.zeros_like(self.enc.flat.data), "dec": torch.zeros_like(self.dec.flat.data)}
         self._klw_host = 0.0                  # host copy of scal[0]
         self._journal = []                    # steps queued since the last host check: (x, kl_weight, noise, update)
         self._committed_base = 0.0            # scal[9] at the last host check
@@ -161,6 +179,30 @@ class AggressiveTextTrainer(object):
 
     def set_lr(self, lr):
         self.scal[1] = lr
+
+    ADAM_STEP = {"enc": 13, "dec": 14}          # scal slots of the two step counts
+
+    def reset_optimizer(self, lr, betas=None):
+        """Re-create both optimizers with learning rate `lr` (toy.py:506-511 after a decay): SGD has no state; Adam's first and
+        second moments and both step counts start from zero again, with `betas` (None keeps the current ones).  Everything
+        queued before is applied first (one host read)."""
+        self.commit()
+        self.scal[1] = lr
+        if self.optimizer != "adam":
+            return
+        if betas is not None and (float(betas[0]), float(betas[1])) != self.betas:
+            self.betas = (float(betas[0]), float(betas[1]))
+            for st in self.static.values():
+                st.graphs = {}                 # the betas are launch arguments of the captured steps
+        self.scal[13:15] = 0
+        for k in ("enc", "dec"):
+            self.adam_m[k].zero_()
+            self.adam_v[k].zero_()
+
+    def adam_steps(self):
+        """(encoder, decoder) Adam step counts (one host read)."""
+        v = self.scal[13:15].cpu().tolist()
+        return int(v[0]), int(v[1])
 
     # how many steps may be queued before the driver looks at the transaction block on its own (one host read)
     JOURNAL_MAX = 64
@@ -405,7 +447,9 @@ class AggressiveTextTrainer(object):
             lib.lv_sum_accum_f32(P(dec_ss), 1, self._s(2), s)
             lib.lv_clip_coef_txn_f32(self._s(2), self.clip, self._s(3), self._s(4), *gate, s)
         # clip_grad_norm_ scales every grad in place; the update only touches the stepped side; both are no-ops under the void flag
-        if update == "both":
+        if self.optimizer == "adam":
+            self._adam_step(update, ef, df)
+        elif update == "both":
             lib.lv_sgd_step_txn_f32(P(ef.data), P(ef.grad), ef.numel, self._s(1), self._s(3), 1, self._s(8), s)
             lib.lv_sgd_step_txn_f32(P(df.data), P(df.grad), df.numel, self._s(1), self._s(3), 1, self._s(8), s)
         else:
@@ -414,6 +458,27 @@ class AggressiveTextTrainer(object):
             if update == "encoder" and self._fold is not None and self.decoder_grads == "norm":
                 b_off, b_n = self._fold.dec_off, self._fold.dec_end - self._fold.dec_off      # what of the decoder's gradient exists
             lib.lv_sgd_step_scale_txn_f32(P(a.data), P(a.grad), a.numel, self._s(1), self._s(3), 1, P(b.grad, b_off), b_n, self._s(8), s)
+
+    def _adam_step(self, update, ef, df):
+        """The Adam twin of the SGD update above: lv_adam_step_txn_f32 per stepped side, the other side's gradient scaled by the
+        clip coefficient in the same launch; every launch is gated by the void flag and ticks its optimizer's step count."""
+        lib, s = self.lib, _eng.stream_ptr(self.device)
+        b1, b2 = self.betas
+        sides = {"enc": ef, "dec": df}
+
+        def args(k):
+            f = sides[k]
+            return (P(f.data), P(f.grad), P(self.adam_m[k]), P(self.adam_v[k]), f.numel, self._s(1), self._s(3),
+                    self._s(self.ADAM_STEP[k]), b1, b2, self.adam_eps, 1)
+        if update == "both":
+            lib.lv_adam_step_txn_f32(*args("enc"), self._s(8), s)
+            lib.lv_adam_step_txn_f32(*args("dec"), self._s(8), s)
+            return
+        a, b = ("enc", df) if update == "encoder" else ("dec", ef)
+        b_off, b_n = 0, b.numel
+        if update == "encoder" and self._fold is not None and self.decoder_grads == "norm":
+            b_off, b_n = self._fold.dec_off, self._fold.dec_end - self._fold.dec_off
+        lib.lv_adam_step_scale_txn_f32(*args(a), P(b.grad, b_off), b_n, self._s(8), s)
 
     def _plan_fold(self, st, update):
         """Norm folding (single GPU, one micro-batch): the three vocabulary-sized gradient tensors -- both embedding tables and
@@ -646,9 +711,12 @@ class AggressiveTextTrainer(object):
         return parts
 
     # -- the loop of text.py:366-400 ------------------------------------------------------------------------
-    def inner_loop(self, batches, first, kl_weight, np_rng=None, max_iter=100, window=15, fixed_k=None, noise_fn=None):
+    def inner_loop(self, batches, first, kl_weight, np_rng=None, max_iter=100, window=15, fixed_k=None, noise_fn=None, next_batch=None):
         """Run the aggressive inner loop starting on batch `first`; later batches are drawn with
         np_rng.random_integers(0, len-1) semantics (text.py:389).  Returns the number of encoder steps taken.
+
+        next_batch: a callable that returns the next batch instead of that draw (toy.py --plot_mode single trains on the same
+        batch throughout and takes no host draw, toy.py:373-374).
 
         fixed_k: run exactly that many steps with no data-dependent exit (BASELINE.json stress config).
 
@@ -669,8 +737,11 @@ class AggressiveTextTrainer(object):
             burn_num_words += (T - 1) * B
             self.step(x, kl_weight, noise=None if noise_fn is None else noise_fn(x), update="encoder")
             steps += 1
-            idx = int(rng.randint(0, len(batches)))
-            x = batches[idx]
+            if next_batch is not None:
+                x = next_batch()
+            else:
+                idx = int(rng.randint(0, len(batches)))
+                x = batches[idx]
             if fixed_k is not None:
                 if steps >= fixed_k:
                     break

@@ -338,3 +338,251 @@ class ImageTrainingLoop(object):
             self.trainer.dec.wgen += 1
         return dict(best_loss=self.best["loss"], best_nll=self.best["nll"], best_kl=self.best["kl"], epochs=len(self.history),
                     history=self.history)
+
+
+class ToyTrainingLoop(object):
+    """Outer training loop of the reference's toy.py (toy.py:235-539), the synthetic experiment behind the posterior-mean plots,
+    around AggressiveTextTrainer.
+
+    The skeleton is text.py's (TextTrainingLoop); what toy.py does differently is reproduced as it is:
+      * `--optim adam`: both halves on torch.optim.Adam(lr=0.001) (the trainer's optimizer="adam"); a learning-rate decay
+        re-creates the optimizers -- with betas (0.5, 0.999) for Adam (toy.py:506-511: trainer.reset_optimizer);
+      * the MI stop check starts from pre_mi = -1, the log line has MI but no active units, there is no `epoch >= 15` gate on the
+        decay, and the per-epoch VAL / TEST lines are toy.test's (four numbers);
+      * plots: `plot_mode` "multiple" records the model posterior mean E[z|x] on the grid (VAE.calc_model_posterior_mean), the
+        inference mean, KL and MI of `plot_data` every `plot_niter` iterations of epoch 0 (eval mode) and at every epoch end (in
+        TRAIN mode under no_grad, before vae.eval(): toy.py:482-483); "single" trains on `plot_data` for every inner and joint
+        step (no host draw picks a batch), follows both means after every step of epoch 0 and returns at the first plot after
+        iteration 0, with no VAL / TEST / IW-NLL;
+      * at the end the best checkpoint is reloaded and the importance-weighted NLL is computed on `iw_batches` (toy.py uses the
+        test set in batches of one sentence).
+    args fields read (toy.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
+    iw_nsamples, optim, plot_mode, num_plot, plot_niter, zmin, zmax, dz.
+
+    plot_data: the (batch, lengths) pair MonoTextData.data_sample returns (toy.py:304), or the batch tensor alone.
+    noise_fn / epoch_hook / np_rng: as TextTrainingLoop's.  plot_dir: when given, every plot is also written as toy.py writes it
+    (`aggr%d_iter%d_multiple.pickle` / `aggr%d_single.pickle`, the keys the reference's plot_scripts read)."""
+
+    LR0 = {"sgd": 1.0, "adam": 0.001}                       # toy.py:284-291
+    DECAY_BETAS = (0.5, 0.999)                              # toy.py:510-511
+
+    def __init__(self, vae, train_batches, val_batches, test_batches, plot_data, args, iw_batches=None, trainer=None, log=print,
+                 np_rng=None, seed=783435, noise_fn=None, epoch_hook=None, plot_dir=None):
+        if getattr(args, "nsamples", 1) != 1:
+            raise ValueError("the fused training step draws one sample per sentence (nsamples = 1, toy.py's default)")
+        self.optim = getattr(args, "optim", "sgd")
+        if self.optim not in self.LR0:
+            raise ValueError("optim: 'sgd' or 'adam' (toy.py:284-291), not %r" % (self.optim,))
+        if args.plot_mode not in ("multiple", "single"):
+            raise ValueError("plot_mode: 'multiple' or 'single'")
+        if args.plot_mode == "single" and not (0 < args.plot_niter < len(train_batches)):
+            # toy.py returns at the first plot after iteration 0; without one in epoch 0 its epoch-end plot call fails
+            raise ValueError("plot_mode 'single' ends at the first plot after iteration 0: plot_niter must be in [1, %d)" % len(train_batches))
+        self.vae, self.args, self.log = vae, args, log
+        self.noise_fn, self.epoch_hook, self.plot_dir = noise_fn, epoch_hook, plot_dir
+        self.train_batches, self.val_batches, self.test_batches = train_batches, val_batches, test_batches
+        self.iw_batches = iw_batches
+        self.plot_x = plot_data[0] if isinstance(plot_data, (tuple, list)) else plot_data
+        self.single = args.plot_mode == "single"
+        self.opt = {"not_improved": 0, "lr": self.LR0[self.optim], "best_loss": 1e4}
+        if trainer is None:
+            trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim)
+        elif getattr(trainer, "optimizer", "sgd") != self.optim:
+            raise ValueError("args.optim is %r but the trainer steps with %r" % (self.optim, getattr(trainer, "optimizer", "sgd")))
+        self.trainer = trainer
+        if hasattr(trainer, "prepare_batches"):
+            trainer.prepare_batches(list(train_batches) + ([self.plot_x] if self.single else []))
+        self.rng = np_rng if np_rng is not None else np.random
+        self.n_train = sum(int(b.shape[0]) for b in train_batches)
+        self.kl_weight = float(args.kl_start)
+        self.anneal_rate = (1.0 - args.kl_start) / (args.warm_up * (self.n_train / args.batch_size))      # toy.py:302
+        from .modules.utils import generate_grid
+        self.grid_z = generate_grid(args.zmin, args.zmax, args.dz, self.plot_x.device, ndim=1)          # toy.py:307,311
+        self.aggressive = bool(args.aggressive)
+        self.iter_ = self.decay_cnt = 0
+        self.pre_mi = -1.0                                                                               # toy.py:296
+        self.best = {"loss": 1e4, "nll": 0.0, "kl": 0.0, "ppl": 0.0, "state": None}
+        self.history, self.iterations, self.mi_checks, self.plots, self.optimizer_resets = [], [], [], [], []
+        self.iw = None
+        self._post, self._infer = [], []          # single mode: the two means after every step of epoch 0
+
+    # -- plots (toy.py:188-231) ---------------------------------------------------------------------------------------------------
+    def _save(self, name, data):
+        if self.plot_dir is None:
+            return
+        import os
+        import pickle
+        os.makedirs(self.plot_dir, exist_ok=True)
+        with open(os.path.join(self.plot_dir, name), "wb") as fh:
+            pickle.dump(data, fh)
+
+    def plot_multiple(self, iter_, where):
+        """toy.py:188-218 (no_grad and the train / eval mode are the caller's, as in toy.py)."""
+        vae, args = self.vae, self.args
+        parts = []
+        kl_sum = mi_sum = 0.0
+        n = 0
+        for data in torch.chunk(self.plot_x, round(args.num_plot / args.batch_size)):
+            kl_sum += vae.KL(data).sum().item()
+            n += data.size(0)
+            mi_sum += vae.calc_mi_q(data) * data.size(0)
+            post = vae.calc_model_posterior_mean(data, self.grid_z)
+            parts.append(torch.cat([post, vae.calc_infer_mean(data)], 1))
+        both = torch.cat(parts, 0)
+        data = {"posterior": both[:, 0].cpu().numpy(), "inference": both[:, 1].cpu().numpy(), "kl": kl_sum / n, "mi": mi_sum / n}
+        self.plots.append(dict(data, iter=iter_, where=where, train_mode=vae.training))
+        self._save("aggr%d_iter%d_multiple.pickle" % (args.aggressive, iter_), data)
+
+    def plot_single(self):
+        """toy.py:220-231: the two means of plot_data after every step of epoch 0, one column per step."""
+        data = {"posterior": torch.cat(self._post, 1).cpu().numpy(), "inference": torch.cat(self._infer, 1).cpu().numpy()}
+        self.plots.append(dict(data, iter=self.iter_, where="single", train_mode=self.vae.training))
+        self._save("aggr%d_single.pickle" % self.args.aggressive, data)
+
+    # -- policy pieces ------------------------------------------------------------------------------------------------------------
+    def _eval_mi(self, batches):
+        self.vae.eval()
+        with torch.no_grad():
+            mi = guarded_eval(self.vae, lambda: E.calc_mi(self.vae, batches), self.log)
+        self.vae.train()
+        return mi
+
+    def check_aggressive(self):
+        """toy.py:466-474: called when a full epoch worth of iterations has passed while aggressive."""
+        cur_mi = self._eval_mi(self.val_batches)
+        self.mi_checks.append((self.pre_mi, cur_mi))
+        if cur_mi - self.pre_mi < 0:
+            self.aggressive = False
+            self.log("STOP BURNING")
+        self.pre_mi = cur_mi
+
+    def end_of_epoch(self, epoch, loss, nll, kl, ppl):
+        """toy.py:489-517 (no `epoch >= 15` gate; a decay re-creates the optimizers).  Returns True when training should stop."""
+        if loss < self.best["loss"]:
+            self.log("update best loss")
+            self.best.update(loss=loss, nll=nll, kl=kl, ppl=ppl, state=copy.deepcopy(self.vae.state_dict()))
+        if loss > self.opt["best_loss"]:
+            self.opt["not_improved"] += 1
+            if self.opt["not_improved"] >= DECAY_EPOCH:
+                self.opt["best_loss"] = loss
+                self.opt["not_improved"] = 0
+                self.opt["lr"] *= LR_DECAY
+                self.vae.load_state_dict(self.best["state"])
+                self.log("new lr: %f" % self.opt["lr"])
+                self.decay_cnt += 1
+                betas = self.DECAY_BETAS if self.optim == "adam" else None
+                self.trainer.reset_optimizer(self.opt["lr"], betas=betas)
+                self.optimizer_resets.append(dict(epoch=epoch, lr=self.opt["lr"], betas=betas))
+        else:
+            self.opt["not_improved"] = 0
+            self.opt["best_loss"] = loss
+        return self.decay_cnt == MAX_DECAY
+
+    def _test(self, batches, mode):
+        """toy.test (toy.py:111-149): eval mode and no_grad are the caller's.  Returns (loss, nll, kl, ppl, mi)."""
+        loss, nll, kl, ppl, mi = guarded_eval(
+            self.vae, lambda: E.test(self.vae, batches, mode, self.args, verbose=False, np_rng=self.rng), self.log)
+        self.log("%s --- avg_loss: %.4f, kl: %.4f, mi: %.4f, recon: %.4f, nll: %.4f, ppl: %.4f" % (mode, loss, kl, mi, nll - kl, nll, ppl))
+        return loss, nll, kl, ppl, mi
+
+    def _result(self, early):
+        return dict(best_loss=self.best["loss"], best_nll=self.best["nll"], best_kl=self.best["kl"], best_ppl=self.best["ppl"],
+                    epochs=len(self.history), history=self.history, iterations=self.iterations, plots=self.plots,
+                    iw_nll=None if self.iw is None else self.iw[0], iw_ppl=None if self.iw is None else self.iw[1],
+                    early_return=early, optimizer_resets=self.optimizer_resets)
+
+    # -- the loop -----------------------------------------------------------------------------------------------------------------
+    def run(self):
+        args, tr, vae = self.args, self.trainer, self.vae
+        log_niter = max(1, (self.n_train // args.batch_size) // 10)                                   # toy.py:268
+        x_plot = self.plot_x
+        start = time.time()
+        vae.train()
+        if self.single:
+            # toy.py:316-317: before the loop, in train mode with autograd on (the generic grid route)
+            self._post.append(vae.calc_model_posterior_mean(x_plot, self.grid_z).detach())
+            self._infer.append(vae.calc_infer_mean(x_plot).detach())
+        next_batch = (lambda: x_plot) if self.single else None
+        for epoch in range(args.epochs):
+            if self.epoch_hook is not None:
+                self.epoch_hook(self, epoch)
+            rep_rec = rep_kl = 0.0
+            rep_sents = 0
+            for i in self.rng.permutation(len(self.train_batches)):
+                batch = x_plot if self.single else self.train_batches[i]
+                rep_sents += int(batch.shape[0])
+                self.kl_weight = min(1.0, self.kl_weight + self.anneal_rate)
+                inner = 0
+                if self.aggressive:
+                    inner = tr.inner_loop(self.train_batches, batch, self.kl_weight, np_rng=self.rng, noise_fn=self.noise_fn,
+                                          next_batch=next_batch)
+                if self.single and epoch == 0 and self.aggressive:                                  # toy.py:391-396
+                    vae.eval()
+                    with torch.no_grad():
+                        self._post.append(self._post[-1])
+                        self._infer.append(vae.calc_infer_mean(x_plot))
+                    vae.train()
+                tr.reset_stats()
+                tr.step(batch, self.kl_weight, noise=None if self.noise_fn is None else self.noise_fn(batch),
+                        update="decoder" if self.aggressive else "both")
+                if self.single and epoch == 0:                                                       # toy.py:417-426
+                    vae.eval()
+                    with torch.no_grad():
+                        self._post.append(vae.calc_model_posterior_mean(x_plot, self.grid_z))
+                        self._infer.append(self._infer[-1] if self.aggressive else vae.calc_infer_mean(x_plot))
+                    vae.train()
+                st = tr.read_stats()
+                rep_rec += st["rec_sum"]
+                rep_kl += st["kl_sum"]
+                self.iterations.append(dict(epoch=epoch, iter=self.iter_, batch=int(i), kl_weight=self.kl_weight,
+                                            aggressive=self.aggressive, inner_steps=inner, rec_sum=st["rec_sum"], kl_sum=st["kl_sum"]))
+                if self.iter_ % log_niter == 0:
+                    train_loss = (rep_rec + rep_kl) / rep_sents
+                    if self.aggressive or epoch == 0:
+                        mi = self._eval_mi(self.val_batches)
+                        self.log("epoch: %d, iter: %d, avg_loss: %.4f, kl: %.4f, mi: %.4f, recon: %.4f,time elapsed %.2fs" % (
+                            epoch, self.iter_, train_loss, rep_kl / rep_sents, mi, rep_rec / rep_sents, time.time() - start))
+                    else:
+                        self.log("epoch: %d, iter: %d, avg_loss: %.4f, kl: %.4f, recon: %.4f,time elapsed %.2fs" % (
+                            epoch, self.iter_, train_loss, rep_kl / rep_sents, rep_rec / rep_sents, time.time() - start))
+                    rep_rec = rep_kl = 0.0
+                    rep_sents = 0
+                if self.iter_ % args.plot_niter == 0 and epoch == 0:                                 # toy.py:453-462
+                    vae.eval()
+                    with torch.no_grad():
+                        if self.single and self.iter_ != 0:
+                            self.plot_single()
+                            return self._result(early=True)          # toy.py:458: no VAL / TEST / IW-NLL
+                        elif not self.single:
+                            self.plot_multiple(self.iter_, "iter")
+                    vae.train()
+                self.iter_ += 1
+                if self.aggressive and self.iter_ % len(self.train_batches) == 0:
+                    self.check_aggressive()
+            self.log("kl weight %.4f" % self.kl_weight)
+            self.log("epoch: %d, VAL" % epoch)
+            with torch.no_grad():
+                self.plot_multiple(self.iter_, "epoch")          # toy.py:482-483: still in train mode
+            vae.eval()
+            with torch.no_grad():
+                loss, nll, kl, ppl, mi = self._test(self.val_batches, "VAL")
+            self.history.append(dict(epoch=epoch, loss=loss, nll=nll, kl=kl, ppl=ppl, mi=mi, aggressive=self.aggressive,
+                                     kl_weight=self.kl_weight, lr=self.opt["lr"], best_updated=loss < self.best["loss"]))
+            stop = self.end_of_epoch(epoch, loss, nll, kl, ppl)
+            self.history[-1].update(lr_after=self.opt["lr"], decay_cnt=self.decay_cnt)
+            if stop:
+                break
+            if epoch % args.test_nepoch == 0:
+                with torch.no_grad():
+                    t = self._test(self.test_batches, "TEST")
+                self.history[-1].update(test=t)
+            vae.train()
+        self.log("best_loss: %.4f, kl: %.4f, nll: %.4f, ppl: %.4f" % (self.best["loss"], self.best["kl"], self.best["nll"], self.best["ppl"]))
+        if self.best["state"] is not None:
+            vae.load_state_dict(self.best["state"])                                                     # toy.py:532
+        vae.eval()
+        if self.iw_batches is not None:
+            with torch.no_grad():
+                self.iw = guarded_eval(vae, lambda: E.calc_iwnll(vae, self.iw_batches, args, np_rng=self.rng), self.log)
+            self.log("iw nll: %.4f, iw ppl: %.4f" % self.iw)
+        return self._result(early=False)
