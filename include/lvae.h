@@ -547,6 +547,31 @@ int lv_sigmoid_bce_bwd_f32(const float* logit, const float* x, const float* drec
 int lv_dec_input_fwd_f32(const float* x, const float* zt, float* in5, int B, int npix, int fm, void* stream);
 int lv_dec_input_bwd_f32(const float* din5, float* dzt, int B, int npix, int fm, void* stream);
 
+/* Batched, device-resident beam search for the LSTM decoder (lv_beam.hip; dec_lstm.py:163-268 for B sentences at once).  State
+ * lives in caller-owned buffers laid out [B][K] (K slots per sentence): tok int64, score f32 (-inf = dead slot), h / c as two
+ * [B][K][H] halves (the cell reads one and writes the other; lv_beam_advance_f32 gathers back), meta int32 [B][4] = {n_done, active,
+ * steps taken, reserved}, the completed list done_score f32 [B][K] / done_ref int32 [B][K][2] = (step, rank) in completion order,
+ * trace int32 [Tmax][B][K][3] = (parent slot, word, destination slot or -1) in rank order, margin f32 [B] (smallest gap between the
+ * last accepted and the first rejected candidate so far) and counter int32 [1] (sentences still active).  Candidates are ordered by
+ * score descending, then flat index slot * V + word ascending.  Envelope: K <= 16, K * V < 2^31, B * K <= 8192
+ * (lv_beam_supported; LV_ERR_UNSUPPORTED outside).  An inactive sentence is left untouched by select and advance. */
+int lv_beam_supported(int B, int K, int V);
+long lv_beam_ws_floats(int B, int K, int V);
+int lv_beam_init_f32(const float* h0, const float* c0, float* h, float* c, int64_t* tok, float* score, int* meta,
+                     float* done_score, float* margin, int* counter, int B, int K, int H, int V, int start_tok, void* stream);
+/* logits [B * K][ld] -> pick_score / pick_flat [B][K + 1]: the best K - n_done candidates (logit - lse) + score[slot] in rank order,
+ * then the runner-up; flat = -1 where there is none.  part: lv_beam_ws_floats(B, K, V) floats. */
+int lv_beam_select_f32(const float* logits, long ld, const float* score, const int* meta, float* part, float* pick_score,
+                       int* pick_flat, float* margin, int B, int K, int V, void* stream);
+/* step t (0-based, < Tmax) of dec_lstm.py:232-246 from those picks; (h_src, c_src) -> (h_dst, c_dst) must be different halves */
+int lv_beam_advance_f32(const float* pick_score, const int* pick_flat, const float* h_src, const float* c_src, float* h_dst,
+                        float* c_dst, int64_t* tok, float* score, int* meta, float* done_score, int* done_ref, int* trace,
+                        int* counter, int t, int Tmax, int B, int K, int H, int V, int end_tok, void* stream);
+/* winner = first maximum over completed (completion order) then live slots (slot order): ids int64 [B][Tmax + 1] (<s> in front),
+ * len int32 [B], win_score f32 [B] */
+int lv_beam_backtrace(const float* score, const int* meta, const float* done_score, const int* done_ref, const int* trace,
+                      int64_t* ids, int* len, float* win_score, int B, int K, int Tmax, int start_tok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

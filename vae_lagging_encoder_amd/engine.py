@@ -1697,3 +1697,95 @@ class LSTMDecodeStepper(object):
             addrow = addrow.contiguous().float()
         self.lib.lv_log_softmax_rows_f32(P(logits), logits.stride(0), n, V, P(addrow), P(out), V, stream_ptr(self.device))
         return out
+
+
+class LSTMBeamSearcher(object):
+    """Beam search for all sentences of a batch together, every per-step decision on the device (lv_beam.hip; reference
+    modules/decoders/dec_lstm.py:163-268, which decodes sentence by sentence and decides on the host).
+
+    B sentences x K slots are B * K rows of LSTMDecodeStepper's exact-f32 launch sequence (embedding gather, input product
+    with the z-projection as its addend, the T = 1 cell, the vocabulary product); the cell reads half 0 of the (h, c) workspace
+    and writes half 1, lv_beam_advance_f32 gathers the survivors' rows back into half 0 -- no clone() / copy_() per step.  The
+    z-projection (+ biases) of a row never changes, so it is computed once per call.  Dead slots compute on whatever finite
+    state they last held; their score of -inf keeps them out of every selection.  No host read inside a step: the host reads
+    the one-int active counter every `poll` steps and stops queueing when it is zero; steps queued past that point are
+    no-ops by the kernels' `active` gate, so the result does not depend on `poll`."""
+
+    TMAX = 100                                                       # the reference's `t < 100`
+
+    def __init__(self, stepper, poll=8):
+        self.st = stepper
+        self.device = stepper.device
+        self.poll = poll
+        self.ws = {}
+
+    def supported(self, B, K):
+        V = self.st.eng.dims()[0]
+        return B > 0 and K > 0 and bool(self.st.lib.lv_beam_supported(B, K, V))
+
+    def _w(self, B, K):
+        w = self.ws.get((B, K))
+        if w is None:
+            V, ni, H, nz = self.st.eng.dims()
+            d, T, n = self.device, self.TMAX, B * K
+            w = _NS()
+            w.tok = torch.empty(n, dtype=torch.int64, device=d)
+            w.score = torch.empty(n, dtype=torch.float32, device=d)
+            w.meta = torch.empty(B, 4, dtype=torch.int32, device=d)
+            w.done_score = torch.empty(n, dtype=torch.float32, device=d)
+            w.done_ref = torch.zeros(n, 2, dtype=torch.int32, device=d)
+            w.trace = torch.zeros(T, n, 3, dtype=torch.int32, device=d)
+            w.margin = torch.empty(B, dtype=torch.float32, device=d)
+            w.counter = torch.empty(1, dtype=torch.int32, device=d)
+            w.part = torch.empty(self.st.lib.lv_beam_ws_floats(B, K, V), dtype=torch.float32, device=d)
+            w.pick_score = torch.empty(B, K + 1, dtype=torch.float32, device=d)
+            w.pick_flat = torch.empty(B, K + 1, dtype=torch.int32, device=d)
+            w.ids = torch.empty(B, T + 1, dtype=torch.int64, device=d)
+            w.len = torch.empty(B, dtype=torch.int32, device=d)
+            w.win = torch.empty(B, dtype=torch.float32, device=d)
+            self.ws[(B, K)] = w
+        return w
+
+    def search(self, z2, K, start_tok, end_tok):
+        """z2 [B][nz] -> (ids: list of B int lists with <s> in front, info: dict of numpy arrays score / steps / n_completed /
+        min_margin, one entry per sentence)."""
+        st = self.st
+        B = z2.shape[0]
+        h0, c0 = st.init_state(z2)                                   # refreshes the stepper's view of the parameters
+        V, ni, H, nz = st.eng.dims()
+        v = st.eng.flat.views
+        lib, s = st.lib, stream_ptr(self.device)
+        n, T = B * K, self.TMAX
+        w, sw = self._w(B, K), st._w(B * K)
+        lib.lv_beam_init_f32(P(h0), P(c0), P(sw.hs), P(sw.cs), P(w.tok), P(w.score), P(w.meta), P(w.done_score), P(w.margin),
+                             P(w.counter), B, K, H, V, start_tok, s)
+        zr = z2.contiguous().float().repeat_interleave(K, dim=0)
+        wih = v["lstm.weight_ih_l0"]
+        _gemm(lib, s, 0, 1, n, 4 * H, nz, P(zr), nz, P(wih, ni), ni + nz, P(sw.Zp), 4 * H,
+              add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
+        poll = max(1, int(self.poll))
+        for t in range(T):
+            lib.lv_embed_gather_f32(P(v["embed.weight"]), P(w.tok), 1, None, 1.0, P(sw.X), 1, n, ni, V, s)
+            _gemm(lib, s, 0, 1, n, 4 * H, ni, P(sw.X), ni, P(wih), ni + nz, P(sw.Gx), 4 * H, add1=P(sw.Zp), ld1=4 * H, mod1=n)
+            lib.lv_lstm_fwd_f32(P(sw.Gx), P(v["lstm.weight_hh_l0"]), P(sw.hs), P(sw.cs), P(sw.gates), None, 1.0, None,
+                                P(sw.lstm_ws), 1, n, H, s)
+            _gemm(lib, s, 0, 1, n, V, H, P(sw.hs, n * H), H, P(v["pred_linear.weight"]), H, P(sw.logits), sw.ldl)
+            lib.lv_beam_select_f32(P(sw.logits), sw.ldl, P(w.score), P(w.meta), P(w.part), P(w.pick_score), P(w.pick_flat),
+                                   P(w.margin), B, K, V, s)
+            lib.lv_beam_advance_f32(P(w.pick_score), P(w.pick_flat), P(sw.hs, n * H), P(sw.cs, n * H), P(sw.hs), P(sw.cs),
+                                    P(w.tok), P(w.score), P(w.meta), P(w.done_score), P(w.done_ref), P(w.trace), P(w.counter),
+                                    t, T, B, K, H, V, end_tok, s)
+            if (t + 1) % poll == 0 and t + 1 < T and int(w.counter.item()) == 0:      # the only host read of the loop
+                break
+        lib.lv_beam_backtrace(P(w.score), P(w.meta), P(w.done_score), P(w.done_ref), P(w.trace), P(w.ids), P(w.len), P(w.win),
+                              B, K, T, start_tok, s)
+        # one device-to-host copy: ids | len | meta | the bits of (winner's score, min margin)
+        out = torch.cat((w.ids, w.len.to(torch.int64).unsqueeze(1), w.meta.to(torch.int64),
+                         torch.stack((w.win, w.margin), dim=1).view(torch.int32).to(torch.int64)), dim=1).cpu()
+        lens = out[:, T + 1].tolist()
+        ids = [row[:m] for row, m in zip(out[:, :T + 1].tolist(), lens)]
+        meta = out[:, T + 2:T + 6].numpy()
+        fl = out[:, T + 6:].to(torch.int32).contiguous().view(torch.float32).numpy()
+        info = {"score": fl[:, 0].copy(), "steps": meta[:, 2].copy(), "n_completed": meta[:, 0].copy(),
+                "min_margin": fl[:, 1].copy()}
+        return ids, info

@@ -5,8 +5,10 @@ Same constructor, containers, construction order and state_dict keys (`embed.wei
 embedding gather fused with dropout_in, z-projection folded into the input GEMM epilogue (the cat((embed, z)) is
 never materialised), fused LSTM step kernels with dropout_out in the epilogue, f32 MFMA vocabulary projection,
 row softmax-NLL; hand-written backward.  Generation (beam / greedy / sample decoding, reference lines 163-367;
-SURVEY.md 8f row 4) steps the same kernels one token at a time through engine.LSTMDecodeStepper.
+SURVEY.md 8f row 4) steps the same kernels one token at a time through engine.LSTMDecodeStepper; beam search decodes the
+whole batch together, every decision on the device, through engine.LSTMBeamSearcher (csrc/lv_beam.hip).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -170,10 +172,39 @@ class LSTMDecoder(DecoderBase):
             return st.sample(logits, u)
         return self._roll_out(z, pick)
 
-    def beam_search_decode(self, z, K=5):
-        """Beam search, sentence by sentence (reference dec_lstm.py:163-268): live hypotheses are expanded together, the K -
-        len(completed) best continuations over (hypothesis, word) survive, a hypothesis completes when it emits </s>, the
-        best by total log-probability is returned with <s> in front."""
+    # True: beam_search_decode decodes the whole batch together through engine.LSTMBeamSearcher (lv_beam.hip) when the shape is
+    # inside its envelope; False forces the sentence-by-sentence route below (A/B runs, tests)
+    batched_beam = True
+    beam_poll = 8                # steps between the batched route's reads of the "sentences still active" counter
+
+    def _beam_searcher(self, device):
+        st = self._stepper(device)
+        bs = getattr(self, "_beam", None)
+        if bs is None or bs.st is not st:
+            bs = self._beam = _eng.LSTMBeamSearcher(st)
+        bs.poll = self.beam_poll
+        return bs
+
+    def beam_search_decode(self, z, K=5, return_info=False):
+        """Beam search (reference dec_lstm.py:163-268): live hypotheses are expanded together, the K - len(completed) best
+        continuations over (hypothesis, word) survive, a hypothesis completes when it emits </s>, the best by total
+        log-probability is returned with <s> in front.  With `batched_beam` and a shape inside the kernels' envelope (K <= 16,
+        K * V < 2^31, batch * K <= 8192) all sentences are decoded together with every decision on the device; otherwise
+        sentence by sentence as the reference does.  return_info=True also returns a dict of per-sentence numpy arrays: `score`
+        (the winner's log-probability), `steps`, `n_completed`, `min_margin` (smallest gap, over the sentence's steps, between
+        the last accepted and the first rejected candidate)."""
+        batch_size = z.size(0)
+        if self.batched_beam and batch_size > 0:
+            bs = self._beam_searcher(z.device)
+            if bs.supported(batch_size, K):
+                with torch.no_grad():
+                    ids, info = bs.search(z.reshape(batch_size, -1).float(), K, self.vocab["<s>"], self.vocab["</s>"])
+                decoded = [[self.vocab.id2word(w) for w in row] for row in ids]
+                return (decoded, info) if return_info else decoded
+        return self._beam_search_per_sentence(z, K, return_info)
+
+    def _beam_search_per_sentence(self, z, K=5, return_info=False):
+        """The reference's procedure, sentence by sentence with the decisions on the host (the A/B route of beam_search_decode)."""
         batch_size = z.size(0)
         dev = z.device
         st = self._stepper(dev)
@@ -181,6 +212,7 @@ class LSTMDecoder(DecoderBase):
         V = len(self.vocab)
         end = self.vocab["</s>"]
         decoded = []
+        info = {"score": [], "steps": [], "n_completed": [], "min_margin": []}
         with torch.no_grad():
             h_init, c_init = st.init_state(z2)
             for idx in range(batch_size):
@@ -189,6 +221,7 @@ class LSTMDecoder(DecoderBase):
                 h, c = h_init[idx:idx + 1].clone(), c_init[idx:idx + 1].clone()
                 completed = []
                 t = 0
+                margin = float("inf")
                 while len(completed) < K and t < 100:
                     t += 1
                     n = len(live)
@@ -197,6 +230,10 @@ class LSTMDecoder(DecoderBase):
                     prev = torch.tensor([hyp[1] for hyp in live], dtype=torch.float32, device=dev)
                     scores = st.log_softmax(logits, prev).reshape(-1)
                     log_prob, indexes = torch.topk(scores, K - len(completed))
+                    if return_info and scores.numel() > K - len(completed):
+                        # the accepted set stays topk(K - done)'s; one more candidate only to measure the gap to the first rejected
+                        wider = torch.topk(scores, K - len(completed) + 1)[0]
+                        margin = min(margin, float(log_prob[-1] - wider[-1]))
                     live_ids = (indexes // V).tolist()
                     word_ids = (indexes % V).tolist()
                     new_live, keep_rows = [], []
@@ -212,7 +249,14 @@ class LSTMDecoder(DecoderBase):
                         break
                     rows = torch.tensor(keep_rows, dtype=torch.int64, device=dev)
                     h, c = h.index_select(0, rows), c.index_select(0, rows)
+                n_completed = len(completed)
                 completed.extend(live)
                 best = max(completed, key=lambda hyp: hyp[1]) if completed else ([self.vocab["<s>"]], 0.0)
                 decoded.append([self.vocab.id2word(w) for w in best[0]])
-        return decoded
+                for key, val in (("score", best[1]), ("steps", t), ("n_completed", n_completed), ("min_margin", margin)):
+                    info[key].append(val)
+        if not return_info:
+            return decoded
+        return decoded, {"score": np.asarray(info["score"], dtype=np.float32), "steps": np.asarray(info["steps"], dtype=np.int64),
+                         "n_completed": np.asarray(info["n_completed"], dtype=np.int64),
+                         "min_margin": np.asarray(info["min_margin"], dtype=np.float32)}
