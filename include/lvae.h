@@ -303,6 +303,31 @@ int lv_loss_assemble_rng_f32(const float* nll, const float* kl, const float* kl_
                              float* loss, float* rec, float* rowscale, float* dkl, float* acc, int T, int B,
                              uint64_t* rng_state, uint64_t rng_inc, void* stream);
 
+/* ---- multi-sample training, VAE.loss(x, kl_weight, nsamples = ns) (lv_multisample.hip) -----------------------------------
+ * The reference expands a sentence's word embeddings (after dropout_in) over the ns samples and runs the decoder on B*ns rows,
+ * row b*ns + s (dec_lstm.py:83-99); the word half of the input projection is the same for a sentence's ns rows, so it is
+ * computed on B rows and expanded: gx[t][b*ns + s][:] = gxw[t][b][:] + zp[b*ns + s][:].  gxw [Td][B][C] (X . W_ih[:, :ni]^T),
+ * zp [B*ns][C] (lv_dec_init_f32's z-projection, biases included), gx [Td][B*ns][C]; any column order the two share. */
+int lv_gx_expand_add_f32(const float* gxw, const float* zp, float* gx, int Td, int B, int ns, int C, void* stream);
+/* its backward counterpart (autograd of the .expand in dec_lstm.py:86-89): dgs[t][b][:] = sum_s dg[t][b*ns + s][:], added in
+ * the order s = 0 .. ns-1 in f32; dg [Td][B*ns][C], dgs [Td][B][C] */
+int lv_sample_sum_f32(const float* dg, float* dgs, int Td, int B, int ns, int C, void* stream);
+/* the same on bf16 images with row strides ld_in / ld_out (elements): summed in f32, rounded to nearest even once */
+int lv_sample_sum_b16(const uint16_t* dg, long ld_in, uint16_t* dgs, long ld_out, int Td, int B, int ns, int C, void* stream);
+/* token ids in decoder row order, x_rep[b*ns + s][:] = x[b][:] (the target `tgt.expand(batch, ns, seq).view(-1)` of
+ * dec_lstm.py:135-141): x int64 [B][T] -> x_rep [B*ns][T] */
+int lv_repeat_rows_i64(const int64_t* x, int64_t* x_rep, int B, int T, int ns, void* stream);
+/* lv_loss_assemble_f32 with samples (dec_lstm.py:146-148 `.mean(dim=1)`, vae.py:95-98): nll [T][B*ns];
+ * rec[b] = (1/ns) sum_s sum_t nll[t][b*ns + s]; loss[b] = rec[b] + w*kl[b]; acc_dev[0..2] += sum_b (loss, rec, kl);
+ * rowscale[b*ns + s] = g_loss[b] / ns; dkl[b] = w*g_loss[b].  ns = 1 gives lv_loss_assemble_f32's bits. */
+int lv_loss_assemble_ns_f32(const float* nll, const float* kl, const float* kl_weight_dev, const float* g_loss,
+                            float* loss, float* rec, float* rowscale, float* dkl, float* acc_dev, int T, int B, int ns,
+                            void* stream);
+/* the same + rng_state[1] += rng_inc, as lv_loss_assemble_rng_f32 */
+int lv_loss_assemble_ns_rng_f32(const float* nll, const float* kl, const float* kl_weight_dev, const float* g_loss,
+                                float* loss, float* rec, float* rowscale, float* dkl, float* acc_dev, int T, int B, int ns,
+                                uint64_t* rng_state, uint64_t rng_inc, void* stream);
+
 /* ---- the batch-sized ends of the two LSTM networks, one launch each (lv_head.hip) --------------------------------------
  * LSTMEncoder's head + GaussianEncoderBase.encode (enc_lstm.py:62-64, encoder.py:40-57): mulv = hT . W_lin^T,
  * z = mu + eps*exp(logvar/2), kl = 0.5*sum(mu^2 + exp(logvar) - logvar - 1).  hT [B][H], W_lin [2nz][H], eps/z [B][ns][nz] */

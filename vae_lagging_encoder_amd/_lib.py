@@ -51,6 +51,12 @@ SIGNATURES = {
     "lv_lstm_fwd_f32_ug": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp],
     "lv_loss_assemble_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "lv_loss_assemble_rng_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _vp],
+    "lv_gx_expand_add_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lv_sample_sum_f32": [_vp, _vp, _i, _i, _i, _i, _vp],
+    "lv_sample_sum_b16": [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp],
+    "lv_repeat_rows_i64": [_vp, _vp, _i, _i, _i, _vp],
+    "lv_loss_assemble_ns_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_loss_assemble_ns_rng_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _u64, _vp],
     "lv_enc_head_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_enc_head_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_dec_tail_parts": [_i],

@@ -749,6 +749,51 @@ class _LstmImages(object):
         _gemm16(lib, s, 1, 4 * H, H, TB, P(self.dG), 4 * H, P(self.hT), self.ldr, gW_hh, H, ws=ws)
 
 
+class _LstmImagesMS(object):
+    """The decoder's operand images for multi-sample training (ns > 1 samples per sentence, decoder row bd = b * ns + s): the
+    INPUT side -- embedded rows X, X^T and the sample-summed gate gradients dGs -- lives on Td * B sentence rows, the
+    RECURRENT side -- h_prev^T and the gate gradients dG the BPTT writes -- on Td * B * ns decoder rows.  The two weight
+    gradients no longer share a contraction length (Td * B against Td * B * ns), so _LstmImages' dual product over
+    [X^T ; h_prev^T] does not apply: dW_hh is a product of its own over Td * B * ns rows, dW_ih[:, :ni] and dX run over Td * B rows --
+    as one grouped lv_gemm_b16_pair launch where lv_gemm_b16_pair_supported takes the two shapes, else as two lv_gemm_b16 products
+    (DESIGN.md 3.3)."""
+
+    def __init__(self, c, Td, B, ns, ni, H):
+        self.Td, self.B, self.ns, self.ni, self.H = Td, B, ns, ni, H
+        self.TB, self.TBd = Td * B, Td * B * ns
+        self.ldr, self.ldrd = _round_up(self.TB, 8), _round_up(self.TBd, 8)
+        self.X = c.i16(self.TB, ni)             # dropout_in(embed(x)) rows     [Td*B][ni]
+        self.XT = c.i16(ni, self.ldr)           # ... transposed                 [ni][Td*B]
+        self.hT = c.i16(H, self.ldrd)           # h_{t-1} rows, transposed       [H][Td*B*ns]
+        self.dG = c.i16(self.TBd, 4 * H)        # gate pre-activation grads      [Td*B*ns][4H]
+        self.dGs = c.i16(self.TB, 4 * H)        # ... summed over the samples    [Td*B][4H]
+
+    def forward(self, lib, s, W16, Gxw, gather):
+        """Gxw[t*B + b][4u + g] = X[t*B + b] . W_ih[g*H + u][:ni] -- the word half of the input projection, no addend (the
+        z-projection and the biases are added per decoder row by lv_gx_expand_add_f32)."""
+        emb, ids, ids_stride, keep, kscale, T, B, V = gather
+        lib.lv_embed_gather_b16(emb, ids, ids_stride, keep, kscale, T, B, self.ni, V, P(self.X), self.ni, P(self.XT), self.ldr, s)
+        _gemm16(lib, s, 0, self.TB, 4 * self.H, self.ni, P(self.X), self.ni, W16, self.ni, Gxw, 4 * self.H)
+
+    def backward(self, lib, s, dG, h_prev, WT16, dX, gW_ih, ld_gw, gW_hh, ws=None):
+        """Arguments as _LstmImages.backward; dG must be None: self.dG holds the BPTT's bf16 gate gradients.  dGs = sum over samples (f32 sum, one rounding); dX = dGs . W_ih[:, :ni]
+        and dW_ih[:, :ni] = dGs^T . X on Td * B rows; dW_hh = dG^T . h_prev on Td * B * ns rows."""
+        assert dG is None
+        ni, H = self.ni, self.H
+        lib.lv_sample_sum_b16(P(self.dG), 4 * H, P(self.dGs), 4 * H, self.Td, self.B, self.ns, 4 * H, s)
+        wsd = ws if ws is not None else _gemm_ws(lib, s)
+        if PAIR_WGRAD and lib.lv_gemm_b16_pair_supported(1, 4 * H, ni, self.TB, 0, self.TB, ni, 4 * H, wsd.numel()):
+            # the two Td * B-row products in one grouped launch (single-destination first product: nsplit0 = 0)
+            with _prof("gemm_bf16", 4.0 * 4 * H * ni * self.TB):
+                lib.lv_gemm_b16_pair(1, 4 * H, ni, self.TB, P(self.dGs), 4 * H, P(self.XT), self.ldr, gW_ih, ld_gw, 0, None, 0,
+                                     0, self.TB, ni, 4 * H, P(self.dGs), 4 * H, WT16, 4 * H, dX, ni, P(wsd), wsd.numel(), s)
+        else:
+            _gemm16(lib, s, 0, self.TB, ni, 4 * H, P(self.dGs), 4 * H, WT16, 4 * H, dX, ni, ws=ws)
+            _gemm16(lib, s, 1, 4 * H, ni, self.TB, P(self.dGs), 4 * H, P(self.XT), self.ldr, gW_ih, ld_gw, ws=ws)
+        lib.lv_cvt_bf16_f32(h_prev, H, self.TBd, H, None, 0, P(self.hT), self.ldrd, s)
+        _gemm16(lib, s, 1, 4 * H, H, self.TBd, P(self.dG), 4 * H, P(self.hT), self.ldrd, gW_hh, H, ws=ws)
+
+
 def _wgrad(lib, s, M, N, K, A, lda, Bm, ldb, C, ldc, prec, ws=None):
     """Weight gradient C[M,N] = A^T . B with A stored [K][M] (lda) and B stored [K][N] (ldb).
 
@@ -1209,17 +1254,26 @@ class LSTMDecoderEngine(object):
         nz = self.m.trans_linear.weight.shape[1]
         return V, ni, H, nz
 
-    def _ws(self, Bd, Td):
+    def _ws(self, Bd, Td, ns=1):
+        """Workspace of a step on Bd decoder rows; ns > 1: Bd = B * ns rows of which each ns share a sentence -- a key of its own
+        ((B, ns, Td): never the buffers of an ns = 1 step on B * ns sentences), input-side buffers on the B sentence rows."""
         V, ni, H, nz = self.dims()
         c = self.wsc
         ldl = _round_up(V, 32)
+        Bs = Bd // ns                      # sentence rows: the embedding gather / scatter and their token sort
+        key = (Bd, Td) if ns == 1 else (Bs, ns, Td)
 
         def build():
             w = _DecWS()
             w.ldl = ldl
             w._alloc = lambda: c.f32(Td * Bd, ldl)
-            w._grew = lambda nb: c.grew((Bd, Td), nb)
-            w.X = c.f32(Td * Bd, ni)
+            w._grew = lambda nb: c.grew(key, nb)
+            w.X = c.f32(Td * Bs, ni)
+            if ns > 1:
+                w.Gxw = c.f32(Td * Bs, 4 * H)          # X . W_ih[:, :ni]^T, one row per (t, sentence)
+                w.dGs = c.f32(Td * Bs, 4 * H)          # gate gradients summed over a sentence's samples (f32 configuration)
+                w.x_rep = torch.empty(Bd, Td + 1, dtype=torch.int64, device=c.device)     # token ids in decoder row order
+                w.Zp_um = c.f32(Bd, 4 * H)             # Zp in unit-major order where the GEMM-based init produced it gate-major
             w.Zp = c.f32(Bd, 4 * H)
             w.Gx = c.f32(Td * Bd, 4 * H)
             w.hs = c.f32(Td + 1, Bd, H)
@@ -1235,36 +1289,37 @@ class LSTMDecoderEngine(object):
             w.dGsum = c.f32(Bd, 4 * H)
             w.lstm_ws = c.f32(self.lib.lv_lstm_ws_floats(Bd, H))
             w.dc0 = c.f32(Bd, H)
-            w.dX = c.f32(Td * Bd, ni)
+            w.dX = c.f32(Td * Bs, ni)
             w.dz = c.f32(Bd, nz)
             w.dz_parts = self.lib.lv_dec_tail_parts(H)
             w.dzp = c.f32(w.dz_parts, Bd, nz)
-            w.srows = c.i32(Td * Bd)
-            w.stok = c.i32(Td * Bd)
-            w.stmp = c.i32(2 * Td * Bd)
+            w.srows = c.i32(Td * Bs)
+            w.stok = c.i32(Td * Bs)
+            w.stmp = c.i32(2 * Td * Bs)
             w.zero1 = torch.zeros(1, dtype=torch.float32, device=c.device)
             w.klz = torch.zeros(Bd, dtype=torch.float32, device=c.device)
             w.loss = c.f32(Bd)
             return w
-        return c.get((Bd, Td), build)
+        return c.get(key, build)
 
-    def fold_parts(self, B, Td):
+    def fold_parts(self, B, Td, ns=1):
         """As TextEncoderEngine.fold_parts: the embedding table's gradient from the scatter and, where the bf16 product takes the
-        256 x 256 tile, dW_pred from its own epilogue (the ws size enters the tile plan, so it must be the launch's)."""
+        256 x 256 tile, dW_pred from its own epilogue (the ws size enters the tile plan, so it must be the launch's).  ns > 1: the
+        scatter runs on the B sentences, dW_pred contracts over the B * ns decoder rows."""
         out = {"embed": self.lib.lv_embed_scatter_sumsq_parts(Td, B)}
         V, ni, H, nz = self.dims()
-        if self._b16(B, Td) is not None:
+        if self._b16(B * ns, Td, ns) is not None:
             dev = self.flat.device
             on_side = torch.device(dev).type == "cuda" and self._overlap_on()
             ws_n = (1 << 26) if on_side else _gemm_ws(self.lib, stream_ptr(dev)).numel()
-            n = self.lib.lv_gemm_b16_sumsq_parts(V, H, Td * B, ws_n)
+            n = self.lib.lv_gemm_b16_sumsq_parts(V, H, Td * B * ns, ws_n)
             if n > 0:
                 out["pred"] = n
         return out
 
-    def _b16(self, Bd, Td):
+    def _b16(self, Bd, Td, ns=1):
         """bf16 images of the vocabulary-sized GEMMs' operands (throughput path), or None when the shapes do not meet
-        lv_gemm_b16's 16-byte row alignment (then lv_gemm_bf16 rounds the f32 operands on the fly)."""
+        lv_gemm_b16's 16-byte row alignment (then lv_gemm_bf16 rounds the f32 operands on the fly).  ns: see _ws."""
         V, ni, H, nz = self.dims()
         if self.precision != "bf16" or not self.native16 or H % 8 != 0:
             return None
@@ -1284,7 +1339,7 @@ class LSTMDecoderEngine(object):
             b.part = c.f32(Td * Bd, 2 * b.nparts)
             b.tgt = c.f32(Td * Bd)
             return b
-        return c.get(("b16", Bd, Td), build)
+        return c.get(("b16", Bd, Td) if ns == 1 else ("b16", Bd // ns, ns, Td), build)
 
     def refresh_weight_images(self, B, device):
         """See LSTMEncoderEngine.refresh_weight_images; covers pred_linear.weight as well."""
@@ -1298,51 +1353,77 @@ class LSTMDecoderEngine(object):
             torch.device(device).type == "cuda" and torch.cuda.get_device_properties(device).multi_processor_count >= 256
         return _weight_images(self, self.lib, stream_ptr(device), device, persist, lstm=use_lstm, pred=use_pred)
 
-    def _lstm_images(self, Bd, Td):
+    def _lstm_images(self, Bd, Td, ns=1):
         V, ni, H, nz = self.dims()
         if not _LstmImages.usable(self.precision, self.native16, ni, H):
             return None
+        if ns > 1:
+            return self.wsc.get(("b16lstm", Bd // ns, ns, Td), lambda: _LstmImagesMS(self.wsc, Td, Bd // ns, ns, ni, H))
         return self.wsc.get(("b16lstm", Bd, Td), lambda: _LstmImages(self.wsc, Td * Bd, ni, H, key=("b16lstm", Bd, Td)))
 
     def forward(self, x, z, mask_in, mask_out, p_in, p_out, want_rec=True, x_key=None):
-        """x int64 [B][T]; z [B][1][nz] (ns = 1 on the HIP path); masks uint8 keep-masks in the reference's
-        batch-first layout ([B][T-1][ni], [B][T-1][H]) or None (eval mode).  Returns rec [B].  x_key: see LSTMEncoderEngine.forward."""
+        """x int64 [B][T]; z [B][ns][nz]; masks uint8 keep-masks in the reference's batch-first layout or None (eval mode):
+        mask_in [B][T-1][ni] -- one per SENTENCE, dropout_in acts before the expansion over the samples (dec_lstm.py:81-89) --,
+        mask_out [B*ns][T-1][H], one per decoder row bd = b * ns + s.  Returns rec per decoder row [B*ns] (ns = 1: rec [B]; the mean
+        over a sentence's rows is dec_lstm.py:146-148's value).  x_key: see LSTMEncoderEngine.forward.
+
+        ns > 1: everything behind the input projection is the ns = 1 code on Bd = B * ns rows; the word half of the
+        input projection is shared by a sentence's samples -- gather (+ dropout_in) and X . W_ih[:, :ni]^T on Td * B rows, expanded
+        and joined with the per-row z-projection by lv_gx_expand_add_f32 -- and the targets are the token ids repeated into decoder
+        row order (w.x_rep)."""
         assert x.dtype == torch.int64 and x.dim() == 2
         x = x.contiguous()
         B, T = x.shape
         Td = T - 1
-        if z.dim() != 3 or z.shape[1] != 1:
-            raise _lib.LvaeError("the HIP decoder path takes nsamples == 1 (z of shape [B,1,nz]); got %s" % (tuple(z.shape),))
-        z2 = z.reshape(B, -1).contiguous()
+        if z.dim() != 3 or z.shape[0] != B or z.shape[1] < 1:
+            raise _lib.LvaeError("the HIP decoder path takes z of shape [B, nsamples, nz]; got %s for a batch of %d" % (tuple(z.shape), B))
+        ns = int(z.shape[1])
+        Bd = B * ns
+        z2 = z.reshape(Bd, -1).contiguous()
         f = self.ensure(x.device)
         lib, s = self.lib, stream_ptr(x.device)
         V, ni, H, nz = self.dims()
-        w = self._ws(B, Td)
+        w = self._ws(Bd, Td, ns)
         v = f.views
         sc_in = 1.0 / (1.0 - p_in) if mask_in is not None else 1.0
         sc_out = 1.0 / (1.0 - p_out) if mask_out is not None else 1.0
         if mask_in is not None:
             assert mask_in.dtype == torch.uint8 and tuple(mask_in.shape) == (B, Td, ni) and mask_in.is_contiguous()
         if mask_out is not None:
-            assert mask_out.dtype == torch.uint8 and tuple(mask_out.shape) == (B, Td, H) and mask_out.is_contiguous()
+            assert mask_out.dtype == torch.uint8 and tuple(mask_out.shape) == (Bd, Td, H) and mask_out.is_contiguous()
         gather = (P(v["embed.weight"]), P(x), T, P(mask_in), sc_in, Td, B, V)
-        if self._lstm_images(B, Td) is None:
+        img = self._lstm_images(Bd, Td, ns)
+        if img is None:
             lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, P(mask_in), sc_in, P(w.X), Td, B, ni, V, s)
-        self._sort = _sorted_tokens(self, lib, s, x, x_key, T, Td, B, V, w)
+        self._sort = _sorted_tokens(self, lib, s, x, x_key, T, Td, B, V, w)      # the SENTENCES' tokens (prepare_batches' list)
+        ids = x
+        if ns > 1:
+            lib.lv_repeat_rows_i64(P(x), P(w.x_rep), B, T, ns, s)
+            ids = w.x_rep
         # c0 = z W_trans^T ; h0 = tanh(c0) (dec_lstm.py:99-101) ; Zp = z W_ih[:, ni:]^T + b_ih + b_hh, so that
-        # Gx = X W_ih[:, :ni]^T + Zp[b]   (cat((word_embed, z_)) never materialised) -- one launch
+        # Gx = X W_ih[:, :ni]^T + Zp[bd]   (cat((word_embed, z_)) never materialised) -- one launch
         wih = v["lstm.weight_ih_l0"]
-        img = self._lstm_images(B, Td)
-        fused = fused_ends_ok(B, nz)
+        fused = fused_ends_ok(Bd, nz)
         if fused:
             lib.lv_dec_init_f32(P(z2), P(v["trans_linear.weight"]), P(wih), ni + nz, ni, P(v["lstm.bias_ih_l0"]),
-                                P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 1 if img is not None else 0, B, H, nz, s)
+                                P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 1 if img is not None else 0, Bd, H, nz, s)
         else:
-            _gemm(lib, s, 0, 1, B, H, nz, P(z2), nz, P(v["trans_linear.weight"]), nz, P(w.cs), H)
-            lib.lv_tanh_f32(P(w.cs), P(w.hs), B * H, s)
-            _gemm(lib, s, 0, 1, B, 4 * H, nz, P(z2), nz, P(wih, ni), ni + nz, P(w.Zp), 4 * H,
+            _gemm(lib, s, 0, 1, Bd, H, nz, P(z2), nz, P(v["trans_linear.weight"]), nz, P(w.cs), H)
+            lib.lv_tanh_f32(P(w.cs), P(w.hs), Bd * H, s)
+            _gemm(lib, s, 0, 1, Bd, 4 * H, nz, P(z2), nz, P(wih, ni), ni + nz, P(w.Zp), 4 * H,
                   add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
-        if img is not None:
+        if ns > 1:
+            zp = w.Zp
+            if img is not None and not fused:             # the image path's recurrences read Gx unit-major (4u + g)
+                lib.lv_gate_interleave_f32(P(w.Zp), None, Bd, H, P(w.Zp_um), s)
+                zp = w.Zp_um
+            if img is not None:
+                wi = self.refresh_weight_images(Bd, x.device)
+                img.forward(lib, s, P(wi.W), P(w.Gxw), gather)
+            else:
+                _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(wih), ni + nz, P(w.Gxw), 4 * H, prec=self.precision)
+            lib.lv_gx_expand_add_f32(P(w.Gxw), P(zp), P(w.Gx), Td, B, ns, 4 * H, s)
+        elif img is not None:
             wi = self.refresh_weight_images(B, x.device)
             if fused:
                 img.forward(lib, s, None, P(wi.W), P(w.Gx), None, None, B, self.wsc, addend_um=P(w.Zp), gather=gather)
@@ -1351,40 +1432,41 @@ class LSTMDecoderEngine(object):
         else:
             _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(wih), ni + nz, P(w.Gx), 4 * H,
                   add1=P(w.Zp), ld1=4 * H, mod1=B, prec=self.precision)
-        b16 = self._b16(B, Td)
+        b16 = self._b16(Bd, Td, ns)
         # persistent recurrence: dropout_out is applied while the output is converted to its bf16 images (mask loads along H)
         # instead of inside the recurrence (8 bytes per row and step: +0.3 us per timestep); same arithmetic, same bits
-        late_mask = b16 is not None and _persistent_ok(self, img, B, H, x.device, _PERSIST_MAX_B)
-        with _prof("lstm_fwd_dec", float(Td), 1 if _persistent_ok(self, img, B, H, x.device, _PERSIST_MAX_B) else Td):
+        late_mask = b16 is not None and _persistent_ok(self, img, Bd, H, x.device, _PERSIST_MAX_B)
+        with _prof("lstm_fwd_dec", float(Td), 1 if _persistent_ok(self, img, Bd, H, x.device, _PERSIST_MAX_B) else Td):
             if late_mask:
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, B, H, x.device)
+                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, Bd, H, x.device)
             else:
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, B, H, x.device)
+                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device)
         if b16 is not None:
             if late_mask and mask_out is not None:
-                lib.lv_cvt_bf16_keep_f32(P(w.hs, B * H), H, Td, B, H, P(mask_out), sc_out, P(b16.O), H, P(b16.OT), b16.ldr, s)
+                lib.lv_cvt_bf16_keep_f32(P(w.hs, Bd * H), H, Td, Bd, H, P(mask_out), sc_out, P(b16.O), H, P(b16.OT), b16.ldr, s)
             elif late_mask:
-                lib.lv_cvt_bf16_f32(P(w.hs, B * H), H, Td * B, H, P(b16.O), H, P(b16.OT), b16.ldr, s)
+                lib.lv_cvt_bf16_f32(P(w.hs, Bd * H), H, Td * Bd, H, P(b16.O), H, P(b16.OT), b16.ldr, s)
             else:
-                lib.lv_cvt_bf16_f32(P(w.O), H, Td * B, H, P(b16.O), H, P(b16.OT), b16.ldr, s)
-            wi = self.refresh_weight_images(B, x.device)
+                lib.lv_cvt_bf16_f32(P(w.O), H, Td * Bd, H, P(b16.O), H, P(b16.OT), b16.ldr, s)
+            wi = self.refresh_weight_images(Bd, x.device)
             if self.fused_nll:
                 # logits leave the GEMM once, as binary16, with the online-softmax statistics taken in its epilogue
-                with _prof("gemm_bf16", 2.0 * Td * B * V * H):
-                    lib.lv_gemm_b16_nll(Td * B, V, H, P(b16.O), H, P(wi.pred), H, P(b16.l16), b16.ldv, P(x), T, 1, B,
+                with _prof("gemm_bf16", 2.0 * Td * Bd * V * H):
+                    lib.lv_gemm_b16_nll(Td * Bd, V, H, P(b16.O), H, P(wi.pred), H, P(b16.l16), b16.ldv, P(ids), T, 1, Bd,
                                         P(b16.part), P(b16.tgt), s)
-                lib.lv_softmax_nll_merge_f32(P(b16.part), b16.nparts, P(b16.tgt), P(w.lse), P(w.nll), Td * B, s)
+                lib.lv_softmax_nll_merge_f32(P(b16.part), b16.nparts, P(b16.tgt), P(w.lse), P(w.nll), Td * Bd, s)
             else:
-                _gemm16(lib, s, 0, Td * B, V, H, P(b16.O), H, P(wi.pred), H, P(w.logits), w.ldl)
+                _gemm16(lib, s, 0, Td * Bd, V, H, P(b16.O), H, P(wi.pred), H, P(w.logits), w.ldl)
         else:
-            _gemm(lib, s, 0, 1, Td * B, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
+            _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
         if not (b16 is not None and self.fused_nll):
-            lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(x), T, 1, P(w.lse), P(w.nll), Td, B, V, s)
+            lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
         if want_rec:
-            # rec[b] = sum_t nll[t][b]  (loss assembly kernel with kl weight 0); the fused driver sums nll itself
-            lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, B, s)
+            # rec[bd] = sum_t nll[t][bd]  (loss assembly kernel with kl weight 0); the fused driver sums nll itself
+            lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
         self.gen += 1
         self.last = (x, z2, mask_in, mask_out, sc_in, sc_out, B, T, self.gen)
+        self.last_ns = ns
         return w.rec
 
     def cond_ll_supported(self, T):
@@ -1420,72 +1502,82 @@ class LSTMDecoderEngine(object):
         return out
 
     def backward(self, drec, gen=None, partial_dz=False):
-        """drec [B] = dL/d rec_b -> fills self.flat.grad; returns dz [B][nz] (partial_dz: the tail kernel's partial sums
-        [parts][B][nz] and their count instead)."""
+        """drec [B*ns] = dL/d rec of every decoder row -> fills self.flat.grad; returns dz [B*ns][nz] (partial_dz: the tail kernel's
+        partial sums [parts][B*ns][nz] and their count instead).  ns > 1: the gate gradients are summed over a
+        sentence's samples (lv_sample_sum_*: the backward of the expansion) and dX, dW_ih[:, :ni] and the embedding scatter run on
+        Td * B rows with the sentence-level keep-mask and sorted token list; dW_hh and the batch-sized tail stay on B * ns rows."""
         x, z2, mask_in, mask_out, sc_in, sc_out, B, T, g = self.last
         if gen is not None and gen != g:
             raise _lib.LvaeError("decoder activations were overwritten by a later forward(); the HIP engine keeps "
                                  "one in-flight step per module")
-        Td = T - 1
+        ns = self.last_ns
+        Bd, Td = B * ns, T - 1
         f = self.flat
         lib, s = self.lib, stream_ptr(x.device)
         V, ni, H, nz = self.dims()
-        w = self._ws(B, Td)
+        w = self._ws(Bd, Td, ns)
         v, gv = f.views, f.gviews
         drec = drec.contiguous()
+        if drec.numel() != Bd:
+            raise _lib.LvaeError("backward takes drec per decoder row (%d values for %d samples per sentence), got %d" % (Bd, ns, drec.numel()))
+        ids = x if ns == 1 else w.x_rep
         wih = v["lstm.weight_ih_l0"]
         gwih = gv["lstm.weight_ih_l0"]
         dev = x.device
-        b16 = self._b16(B, Td)
+        b16 = self._b16(Bd, Td, ns)
         if b16 is not None and self.fused_nll:
-            lib.lv_softmax_nll_bwd_h16(P(b16.l16), b16.ldv, P(w.lse), P(x), T, 1, P(drec), P(b16.dl), b16.ldv, Td, B, V, s)
+            lib.lv_softmax_nll_bwd_h16(P(b16.l16), b16.ldv, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
         elif b16 is not None:
-            lib.lv_softmax_nll_bwd_b16(P(w.logits), w.ldl, P(w.lse), P(x), T, 1, P(drec), P(b16.dl), b16.ldv, Td, B, V, s)
+            lib.lv_softmax_nll_bwd_b16(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
         else:
-            lib.lv_softmax_nll_bwd_f32(P(w.logits), w.ldl, P(w.lse), P(x), T, 1, P(drec), Td, B, V, s)
+            lib.lv_softmax_nll_bwd_f32(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), Td, Bd, V, s)
         ctx, sws = self._fork(dev)                    # side: dW_pred = dlogits^T . O (only needs dlogits and O)
         with ctx:
             if b16 is not None and self.fold and "pred" in self.fold:
                 sq, only = self.fold["pred"]          # |dW_pred|^2 leaves the product's own epilogue
                 gws = sws if sws is not None else _gemm_ws(lib, s)
-                if lib.lv_gemm_b16_sumsq_parts(V, H, Td * B, gws.numel()) != sq.numel():
+                if lib.lv_gemm_b16_sumsq_parts(V, H, Td * Bd, gws.numel()) != sq.numel():
                     raise RuntimeError("norm folding: the plan's partial count does not match this launch's tile plan")
-                with _prof("gemm_bf16", 2.0 * V * H * Td * B):
-                    lib.lv_gemm_b16_sumsq(1, V, H, Td * B, P(b16.dl), b16.ldv, P(b16.OT), b16.ldr, P(gv["pred_linear.weight"]), H,
+                with _prof("gemm_bf16", 2.0 * V * H * Td * Bd):
+                    lib.lv_gemm_b16_sumsq(1, V, H, Td * Bd, P(b16.dl), b16.ldv, P(b16.OT), b16.ldr, P(gv["pred_linear.weight"]), H,
                                           P(gws), gws.numel(), P(sq), int(only), stream_ptr(dev))
             elif b16 is not None:
-                _gemm16(lib, stream_ptr(dev), 1, V, H, Td * B, P(b16.dl), b16.ldv, P(b16.OT), b16.ldr,
+                _gemm16(lib, stream_ptr(dev), 1, V, H, Td * Bd, P(b16.dl), b16.ldv, P(b16.OT), b16.ldr,
                         P(gv["pred_linear.weight"]), H, ws=sws)
             else:
-                _wgrad(lib, stream_ptr(dev), V, H, Td * B, P(w.logits), w.ldl, P(w.O), H, P(gv["pred_linear.weight"]), H,
+                _wgrad(lib, stream_ptr(dev), V, H, Td * Bd, P(w.logits), w.ldl, P(w.O), H, P(gv["pred_linear.weight"]), H,
                        self.precision, ws=sws)
-        img = self._lstm_images(B, Td)
-        late_mask = _persistent_ok(self, img, B, H, dev, _PERSIST_BWD_MAX_B)
+        img = self._lstm_images(Bd, Td, ns)
+        late_mask = _persistent_ok(self, img, Bd, H, dev, _PERSIST_BWD_MAX_B)
         if b16 is not None and late_mask and mask_out is not None:
             # dO = dlogits . W_pred with the dropout_out backward applied where the product's K pieces are summed (no pass of its own)
             gws = _gemm_ws(lib, s)
-            with _prof("gemm_bf16", 2.0 * Td * B * H * V):
-                lib.lv_gemm_b16_keep(Td * B, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), P(mask_out), sc_out, B,
+            with _prof("gemm_bf16", 2.0 * Td * Bd * H * V):
+                lib.lv_gemm_b16_keep(Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), P(mask_out), sc_out, Bd,
                                      P(gws), gws.numel(), s)
         else:
             if b16 is not None:
-                _gemm16(lib, s, 0, Td * B, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), H)
+                _gemm16(lib, s, 0, Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), H)
             else:
-                _gemm(lib, s, 0, 0, Td * B, H, V, P(w.logits), w.ldl, P(v["pred_linear.weight"]), H, P(w.dO), H, prec=self.precision)
+                _gemm(lib, s, 0, 0, Td * Bd, H, V, P(w.logits), w.ldl, P(v["pred_linear.weight"]), H, P(w.dO), H, prec=self.precision)
             if late_mask and mask_out is not None:
-                lib.lv_keep_scale_f32(P(w.dO), P(mask_out), sc_out, Td, B, H, s)      # dropout_out backward, once, loads along H
+                lib.lv_keep_scale_f32(P(w.dO), P(mask_out), sc_out, Td, Bd, H, s)      # dropout_out backward, once, loads along H
         with _prof("lstm_bwd_dec", float(Td), 1 if late_mask else 2 * Td):
             _lstm_backward(self, lib, s, img, w, P(w.dO), None, None if late_mask else P(mask_out), 1.0 if late_mask else sc_out,
-                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, B, H, dev)
+                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, Bd, H, dev)
         ctx, sws = self._fork(dev)                    # side: everything that only needs dG (runs under the encoder's backward)
         with ctx:
             s2 = stream_ptr(dev)
-            if img is not None:
+            if img is not None:                        # (_LstmImagesMS for ns > 1: sample sum, then the Td * B-row products)
                 img.backward(lib, s2, None, P(w.hs), P(self._wimg.WT), P(w.dX), P(gwih), ni + nz, P(gv["lstm.weight_hh_l0"]), ws=sws)
             else:
-                _gemm(lib, s2, 0, 0, Td * B, ni, 4 * H, P(w.dG), 4 * H, P(wih), ni + nz, P(w.dX), ni, prec=self.precision, ws=sws)
-                _wgrad(lib, s2, 4 * H, ni, Td * B, P(w.dG), 4 * H, P(w.X), ni, P(gwih), ni + nz, self.precision, ws=sws)
-                _wgrad(lib, s2, 4 * H, H, Td * B, P(w.dG), 4 * H, P(w.hs), H, P(gv["lstm.weight_hh_l0"]), H,
+                dG = w.dG
+                if ns > 1:
+                    lib.lv_sample_sum_f32(P(w.dG), P(w.dGs), Td, B, ns, 4 * H, s2)
+                    dG = w.dGs
+                _gemm(lib, s2, 0, 0, Td * B, ni, 4 * H, P(dG), 4 * H, P(wih), ni + nz, P(w.dX), ni, prec=self.precision, ws=sws)
+                _wgrad(lib, s2, 4 * H, ni, Td * B, P(dG), 4 * H, P(w.X), ni, P(gwih), ni + nz, self.precision, ws=sws)
+                _wgrad(lib, s2, 4 * H, H, Td * Bd, P(w.dG), 4 * H, P(w.hs), H, P(gv["lstm.weight_hh_l0"]), H,
                        self.precision, ws=sws)
             self._aux.join(dev)                        # token sort queued by forward()
             if self.fold and "embed" in self.fold:
@@ -1496,21 +1588,21 @@ class LSTMDecoderEngine(object):
                 lib.lv_embed_scatter_full_f32(P(w.dX), P(mask_in), sc_in, P(self._sort[0]), P(self._sort[1]), Td, B, P(gv["embed.weight"]), ni,
                                               V, V - 1, s2)
         self._mark_pending(dev)
-        if not fused_ends_ok(B, nz):
-            _gemm(lib, s, 1, 0, 4 * H, nz, B, P(w.dGsum), 4 * H, P(z2), nz, P(gwih, ni), ni + nz)
-            lib.lv_colsum_f32(P(w.dGsum), 4 * H, B, 4 * H, P(gv["lstm.bias_ih_l0"]), P(gv["lstm.bias_hh_l0"]), s)
-            _gemm(lib, s, 0, 0, B, nz, 4 * H, P(w.dGsum), 4 * H, P(wih, ni), ni + nz, P(w.dz), nz)
-            _gemm(lib, s, 0, 0, B, nz, H, P(w.dc0), H, P(v["trans_linear.weight"]), nz, P(w.dz), nz, acc=1)
-            _gemm(lib, s, 1, 0, H, nz, B, P(w.dc0), H, P(z2), nz, P(gv["trans_linear.weight"]), nz)
+        if not fused_ends_ok(Bd, nz):
+            _gemm(lib, s, 1, 0, 4 * H, nz, Bd, P(w.dGsum), 4 * H, P(z2), nz, P(gwih, ni), ni + nz)
+            lib.lv_colsum_f32(P(w.dGsum), 4 * H, Bd, 4 * H, P(gv["lstm.bias_ih_l0"]), P(gv["lstm.bias_hh_l0"]), s)
+            _gemm(lib, s, 0, 0, Bd, nz, 4 * H, P(w.dGsum), 4 * H, P(wih, ni), ni + nz, P(w.dz), nz)
+            _gemm(lib, s, 0, 0, Bd, nz, H, P(w.dc0), H, P(v["trans_linear.weight"]), nz, P(w.dz), nz, acc=1)
+            _gemm(lib, s, 1, 0, H, nz, Bd, P(w.dc0), H, P(z2), nz, P(gv["trans_linear.weight"]), nz)
             return (w.dz, 1) if partial_dz else w.dz
         # batch-sized tail in one launch (critical path: dz feeds the encoder's backward): the z-columns of dW_ih, both
         # bias gradients, dW_trans, and dz = dGsum . W_ih[:, ni:] + dc0 . W_trans
         lib.lv_dec_tail_bwd_f32(P(w.dGsum), P(w.dc0), P(z2), P(wih), ni + nz, ni, P(v["trans_linear.weight"]), P(gwih), ni + nz,
                                 P(gv["trans_linear.weight"]), P(gv["lstm.bias_ih_l0"]), P(gv["lstm.bias_hh_l0"]), P(w.dzp),
-                                B, H, nz, s)
+                                Bd, H, nz, s)
         if partial_dz:
             return w.dzp, w.dz_parts         # the fused driver's encoder head sums the parts itself
-        lib.lv_colsum_f32(P(w.dzp), B * nz, w.dz_parts, B * nz, P(w.dz), None, s)
+        lib.lv_colsum_f32(P(w.dzp), Bd * nz, w.dz_parts, Bd * nz, P(w.dz), None, s)
         return w.dz
 
 

@@ -68,8 +68,13 @@ class AggressiveTextTrainer(object):
 
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
                  precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
-        """optimizer = "sgd" (default: optim.SGD(momentum=0), text.py:325-326) or "adam": torch.optim.Adam(lr, betas, eps) on each of
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1):
+        """nsamples = ns > 1: text.py --nsamples, VAE.loss(x, kl_weight, nsamples=ns) (vae.py:79-98) -- ns reparameterised samples per
+        sentence, the decoder on B * ns rows (row b * ns + s), the reconstruction term averaged over the samples; the report sums stay
+        sums over the B sentences.  Noise shapes: eps [B][ns][nz], mask_in [B][T-1][ni] (dropout_in acts before the expansion: one mask
+        per sentence), mask_out [B*ns][T-1][H].  The word half of the decoder's input projection and its backward run once per
+        sentence (engine.LSTMDecoderEngine.forward).  Single GPU, eager mode, one micro-batch, decoder_grads = "full".
+        optimizer = "sgd" (default: optim.SGD(momentum=0), text.py:325-326) or "adam": torch.optim.Adam(lr, betas, eps) on each of
         the two sides, as toy.py --optim adam builds them (toy.py:289-290) -- first and second moments per flat buffer, one step
         count per optimizer in device memory, all behind the transaction gate (lv_adam_step_txn_f32: a voided step moves none of
         them).  `lr` is the learning rate of either optimizer; reset_optimizer() re-creates them (toy.py:506-511).  Single GPU,
@@ -100,6 +105,15 @@ class AggressiveTextTrainer(object):
             raise ValueError("optimizer='adam' runs on a single GPU with micro_batches = 1 (no grad_sync): the Adam step is not "
                              "implemented for data parallelism or gradient accumulation")
         self.optimizer = optimizer
+        self.nsamples = int(nsamples)
+        if self.nsamples < 1:
+            raise ValueError("nsamples must be >= 1, not %r" % (nsamples,))
+        if self.nsamples > 1:
+            fenced = [n for n, on in (("grad_sync", grad_sync is not None), ("use_graph=True", bool(use_graph)),
+                                      ("micro_batches > 1", self.micro_batches > 1), ("decoder_grads='norm'", decoder_grads == "norm")) if on]
+            if fenced:
+                raise ValueError("nsamples = %d runs on a single GPU in eager mode with micro_batches = 1 and decoder_grads = 'full'; "
+                                 "not implemented together with: %s" % (self.nsamples, ", ".join(fenced)))
         self.fold_norm = bool(fold_norm)
         assert decoder_grads in ("full", "norm")
         self.decoder_grads = decoder_grads
@@ -326,17 +340,18 @@ class AggressiveTextTrainer(object):
         else:
             d = self.device
             V, ni, H, nz = self.dec.dims()
+            ns = self.nsamples
             st = _Static()
             st.x = torch.zeros(B, T, dtype=torch.int64, device=d)
-            st.eps = torch.zeros(B, 1, nz, dtype=torch.float32, device=d)
-            st.m_in = torch.ones(B, T - 1, ni, dtype=torch.uint8, device=d)
-            st.m_out = torch.ones(B, T - 1, H, dtype=torch.uint8, device=d)
-            st.z = torch.empty(B, 1, nz, dtype=torch.float32, device=d)
+            st.eps = torch.zeros(B, ns, nz, dtype=torch.float32, device=d)
+            st.m_in = torch.ones(B, T - 1, ni, dtype=torch.uint8, device=d)              # per sentence (dec_lstm.py:81-89)
+            st.m_out = torch.ones(B * ns, T - 1, H, dtype=torch.uint8, device=d)         # per decoder row b * ns + s
+            st.z = torch.empty(B, ns, nz, dtype=torch.float32, device=d)
             st.kl = torch.empty(B, dtype=torch.float32, device=d)
             st.loss = torch.empty(B, dtype=torch.float32, device=d)
             st.rec = torch.empty(B, dtype=torch.float32, device=d)
             st.gl = torch.full((B,), 1.0 / (B * parts), dtype=torch.float32, device=d)   # d(mean_b loss_b)/d loss_b
-            st.rowscale = torch.empty(B, dtype=torch.float32, device=d)
+            st.rowscale = torch.empty(B * ns, dtype=torch.float32, device=d)
             st.dkl = torch.empty(B, dtype=torch.float32, device=d)
             st.dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
             st.graphs = {}
@@ -374,10 +389,17 @@ class AggressiveTextTrainer(object):
         # encoder: ... LSTM, then head + reparameterise + KL in one launch
         mulv = self.enc.forward(st.xin, head=(st.eps, st.z, st.kl), x_key=st.x_key)
         self.dec.forward(st.xin, st.z, m_in, m_out, dec.dropout_in.p, dec.dropout_out.p, want_rec=False, x_key=st.x_key)
-        w = self.dec._ws(B, T - 1)
+        ns = self.nsamples
+        w = self.dec._ws(B * ns, T - 1, ns)
         # rec, loss, the running report sums and the seeds of mean_b(loss_b).backward(), one launch
         # (report sums into the pending slots: committed by the transaction gate; the Philox offset moves on here when drawn)
-        if draw:
+        if ns > 1 and draw:
+            lib.lv_loss_assemble_ns_rng_f32(P(w.nll), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
+                                            self._s(10), T - 1, B, ns, P(self.rng_state), 1, s)
+        elif ns > 1:
+            lib.lv_loss_assemble_ns_f32(P(w.nll), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
+                                        self._s(10), T - 1, B, ns, s)
+        elif draw:
             lib.lv_loss_assemble_rng_f32(P(w.nll), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
                                          self._s(10), T - 1, B, P(self.rng_state), 1, s)
         else:
@@ -493,7 +515,7 @@ class AggressiveTextTrainer(object):
         key = (B, T)
         f = self._fold_plans.get(key)
         if f is None:
-            pe, pd = self.enc.fold_parts(B, T), self.dec.fold_parts(B, T - 1)
+            pe, pd = self.enc.fold_parts(B, T), self.dec.fold_parts(B, T - 1, self.nsamples)
             f = _eng._NS()
             f.n = pe["embed"] + pd["embed"] + pd.get("pred", 0)
             f.parts = torch.zeros(f.n, dtype=torch.float32, device=self.device)
@@ -544,6 +566,8 @@ class AggressiveTextTrainer(object):
         steps): should a persistent recurrence of it time out, the device voids it -- and everything queued behind it -- and the
         read replays the voided steps one rung down the fallback ladder (_settle).  x (and injected noise) must therefore stay
         unmodified until then, as they must for the sorted-token cache."""
+        if self.nsamples > 1 and noise is not None:
+            self._check_noise(x, noise)
         self._queue_step(x, kl_weight, noise, update)
         self._journal.append((x, float(kl_weight), noise, update))
         if len(self._journal) >= self.JOURNAL_MAX:
@@ -680,6 +704,17 @@ class AggressiveTextTrainer(object):
                 self.enc.wgen += 1
             if update in ("decoder", "both"):
                 self.dec.wgen += 1
+
+    def _check_noise(self, x, noise):
+        """nsamples > 1: injected noise must have the multi-sample shapes exactly (a mask_in in the expanded [B*ns][T-1][ni] form
+        would otherwise be copied into the wrong rows) -- refused before anything is launched."""
+        B, T = x.shape
+        V, ni, H, nz = self.dec.dims()
+        ns = self.nsamples
+        want = ((B, ns, nz), (B, T - 1, ni), (B * ns, T - 1, H))
+        for name, got, shape in zip(("eps", "mask_in", "mask_out"), noise, want):
+            if got is not None and tuple(got.shape) != shape:
+                raise ValueError("nsamples = %d: %s must have shape %s, got %s" % (ns, name, shape, tuple(got.shape)))
 
     def _capture(self, st, update, draw):
         """Capture the step as hipGraph(s).  With a gradient all-reduce the step is split around it

@@ -57,7 +57,9 @@ class TextTrainingLoop(object):
     def __init__(self, vae, train_batches, val_batches, test_batches, args, n_train_sentences=None, trainer=None,
                  log=print, np_rng=None, seed=783435, noise_fn=None, epoch_hook=None):
         """noise_fn(x) -> (eps, mask_in, mask_out): injects the random draws of every training step (parity replays of a
-        recorded reference run, tests/test_policy_replay.py); None draws them on the device.
+        recorded reference run, tests/test_policy_replay.py); None draws them on the device.  With args.nsamples = ns > 1
+        (text.py --nsamples) in the multi-sample shapes: eps [B][ns][nz], mask_in [B][T-1][ni], mask_out [B*ns][T-1][H].
+        A `trainer` that is handed in must have been built with the same nsamples.
         epoch_hook(loop, epoch): called at the top of every epoch, before its batch permutation is drawn (checkpoint / resume
         policies; the replay test re-synchronises the weights there)."""
         self.vae, self.args, self.log = vae, args, log
@@ -66,7 +68,11 @@ class TextTrainingLoop(object):
         self.train_batches, self.val_batches, self.test_batches = train_batches, val_batches, test_batches
         if getattr(args, "momentum", 0) != 0:
             raise ValueError("the fused driver implements optim.SGD(momentum=0), the reference's default (text.py:325-326)")
-        self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed)
+        self.nsamples = int(getattr(args, "nsamples", 1))
+        if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
+            raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
+        self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
+                                                                                 nsamples=self.nsamples)
         if hasattr(self.trainer, "prepare_batches"):
             self.trainer.prepare_batches(train_batches)          # per-batch index structures, built once with the batch list
         self.rng = np_rng if np_rng is not None else np.random
