@@ -458,7 +458,9 @@ int lv_argmax_rows_f32(const float* in, long ld, int R, int C, int64_t* idx, voi
 /* F.log_softmax(logits, -1) + the live hypotheses' running log-probabilities addrow[r] (beam_search_decode, dec_lstm.py:214-218) */
 int lv_log_softmax_rows_f32(const float* in, long ld, int R, int C, const float* addrow, float* out, long ldo, void* stream);
 /* categorical draw from softmax(logits[r]) by inverse CDF with the uniform u[r] (sample_decode's torch.multinomial,
- * dec_lstm.py:351-352): idx[r] = first c with cumsum softmax >= u[r] */
+ * dec_lstm.py:351-352).  With w[c] = exp(logits[r][c] - max_c logits[r]) and s = sum_c w[c]: idx[r] = the first column with
+ * w[c] > 0 whose inclusive running sum reaches u[r]*s.  If rounding leaves the running sum short, idx[r] is the last column
+ * with positive weight; C - 1 is returned only if no column has positive weight.  A column of probability zero is never drawn. */
 int lv_sample_rows_f32(const float* in, long ld, int R, int C, const float* u, int64_t* idx, void* stream);
 
 /* ---- Omniglot path: ResNetEncoderV2 (modules/encoders/enc_resnet_v2.py:27-126) and PixelCNNDecoderV2

@@ -208,19 +208,20 @@ def test_lstm_fwd_unit_major_gx(lib, hip_device, T, B, H, use_mask):
     mask = (torch.rand(B, T, H, generator=g) < 0.5).to(torch.uint8).to(dev)
     perm = torch.arange(4 * H).view(4, H).t().reshape(-1).to(dev)
     gxu = gx[:, :, perm].contiguous()
-    outs = []
-    for fn, x in ((lib.lv_lstm_fwd_bf16, gx), (lib.lv_lstm_fwd_bf16_ug, gxu)):
-        hs = torch.zeros(T + 1, B, H, device=dev)
-        cs = torch.zeros(T + 1, B, H, device=dev)
-        hs[0] = 0.1
-        cs[0] = -0.2
-        gates = torch.empty(T, B, 4 * H, device=dev)
-        hdrop = torch.empty(T, B, H, device=dev)
-        ws = torch.empty(lib.lv_lstm_ws_floats(B, H), device=dev)
-        fn(P(x), P(whh), P(hs), P(cs), P(gates), P(mask) if use_mask else None, 2.0, P(hdrop), P(ws), T, B, H, _s(dev))
-        outs.append((hs.cpu(), cs.cpu(), gates.cpu(), hdrop.cpu()))
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
+    for pair in ((lib.lv_lstm_fwd_bf16, lib.lv_lstm_fwd_bf16_ug), (lib.lv_lstm_fwd_f32, lib.lv_lstm_fwd_f32_ug)):
+        outs = []
+        for fn, x in zip(pair, (gx, gxu)):
+            hs = torch.zeros(T + 1, B, H, device=dev)
+            cs = torch.zeros(T + 1, B, H, device=dev)
+            hs[0] = 0.1
+            cs[0] = -0.2
+            gates = torch.empty(T, B, 4 * H, device=dev)
+            hdrop = torch.empty(T, B, H, device=dev)
+            ws = torch.empty(lib.lv_lstm_ws_floats(B, H), device=dev)
+            fn(P(x), P(whh), P(hs), P(cs), P(gates), P(mask) if use_mask else None, 2.0, P(hdrop), P(ws), T, B, H, _s(dev))
+            outs.append((hs.cpu(), cs.cpu(), gates.cpu(), hdrop.cpu()))
+        for a, b in zip(*outs):
+            assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("tA,M,N,K,split", [

@@ -210,12 +210,17 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* __re
     __syncthreads();
     float M = sm[0], S = ss[0];
     for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
-    const float L = M + logf(S) - (addrow ? addrow[r] : 0.f);
-    for (int c = tid; c < C; c += 256) out[(long)r * ldo + c] = in[(long)r * ld + c] - L;
+    // (x - M) - log S, not x - (M + log S): the sum M + log S is rounded at the magnitude of the logits (half an ulp of M), which a
+    // common offset of the row makes arbitrarily larger than the result; x - M is rounded at the magnitude of the difference
+    const float lz = logf(S) - (addrow ? addrow[r] : 0.f);
+    for (int c = tid; c < C; c += 256) out[(long)r * ldo + c] = (in[(long)r * ld + c] - M) - lz;
 }
 
 // categorical draw from softmax(in[r][:]) by inverse CDF with the uniform u[r] in [0,1): single wave per row, two passes
-// (logsumexp, then a blocked running sum); idx[r] = first c with cumsum_c softmax >= u
+// (logsumexp, then a blocked running sum).  With w[c] = exp(in[r][c] - max) and s = sum_c w[c]: idx[r] = the first column with
+// w[c] > 0 whose inclusive running sum reaches u*s.  A column of weight zero (-inf logit, or underflow) is never returned, as
+// torch.multinomial never returns an index of probability zero: when rounding leaves the f32 running sum short of u*s (u close
+// to 1), idx[r] is the LAST column with positive weight; C - 1 is returned only if no column has positive weight.
 __global__ __launch_bounds__(64) void sample_rows_kernel(const float* __restrict__ in, long ld, int R, int C,
                                                          const float* __restrict__ u, int64_t* __restrict__ idx) {
     const int r = (int)blockIdx.x, l = (int)threadIdx.x;
@@ -228,7 +233,8 @@ __global__ __launch_bounds__(64) void sample_rows_kernel(const float* __restrict
     }
     const float target = u[r] * s;                     // in units of exp(x - m)
     float run = 0.f;
-    int found = C - 1;
+    int found = -1;
+    int last_pos = -1;                                 // highest column with positive weight seen so far: the fallback
     bool done = false;
     for (int c0 = 0; c0 < C && !done; c0 += 64) {      // blocks of 64 consecutive columns, inclusive scan inside the wave
         const int c = c0 + l;
@@ -239,18 +245,22 @@ __global__ __launch_bounds__(64) void sample_rows_kernel(const float* __restrict
             const float o = __shfl_up(sc, d, 64);
             if (l >= d) sc += o;
         }
-        const bool hit = c < C && run + sc >= target;
-        // lowest lane that hit
+        const bool hit = p > 0.f && run + sc >= target;      // p > 0 implies c < C
+        // lowest lane that hit, highest lane with positive weight
         int first = hit ? l : 64;
+        int pos = p > 0.f ? c : -1;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
             const int o = __shfl_xor(first, d, 64);
             first = o < first ? o : first;
+            const int q = __shfl_xor(pos, d, 64);
+            pos = q > pos ? q : pos;
         }
         if (first < 64) { found = c0 + first; done = true; }
+        last_pos = pos > last_pos ? pos : last_pos;
         run += __shfl(sc, 63, 64);
     }
-    if (l == 0) idx[r] = found;
+    if (l == 0) idx[r] = found >= 0 ? found : (last_pos >= 0 ? last_pos : C - 1);
 }
 
 }  // namespace
