@@ -395,6 +395,22 @@ int lv_scale_txn_f32(float* x, long n, const float* coef_dev, const float* void_
  * clip_grad_norm_ (text.py:385) scales all the same -- in one launch */
 int lv_sgd_step_scale_txn_f32(float* p, float* g, long n, const float* lr_dev, const float* coef_dev, int write_back_clipped,
                               float* x2, long n2, const float* void_flag_dev, void* stream);
+/* torch.optim.SGD(lr, momentum) with momentum > 0 (text.py --momentum: text.py:30, 325-326, re-created after a decay at 492-493;
+ * dampening 0, no nesterov, no weight decay) over a flat buffer, one velocity element per parameter element in `buf`:
+ *     g' = g * coef;  buf = round(round(buf * momentum) + g');  p = fma(-lr, buf, p)
+ * -- the roundings of torch's buf.mul_(momentum).add_(g') and p.add_(buf, alpha=-lr), so p and buf equal torch's bit for bit.  A zeroed
+ * buf is torch's missing momentum_buffer (first step: buf = g'); re-creating the optimizer is zeroing it.  g' is written back to g when
+ * write_back_clipped and coef != 1.  coef_dev may be NULL (coefficient 1). */
+int lv_sgd_momentum_step_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev, float momentum,
+                             int write_back_clipped, void* stream);
+/* lv_sgd_momentum_step_f32 behind the transaction gate (text.py:385-387 with --momentum in the fused trainer): while
+ * void_flag_dev[0] != 0, p, g and buf keep their bit patterns -- a voided step moves neither the weights nor the velocity. */
+int lv_sgd_momentum_step_txn_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev, float momentum,
+                                 int write_back_clipped, const float* void_flag_dev, void* stream);
+/* lv_sgd_momentum_step_txn_f32 on (p, g, buf) and lv_scale_txn_f32 on x2, the gradient of the side that is NOT stepped (text.py:385
+ * scales it all the same), in one launch */
+int lv_sgd_momentum_step_scale_txn_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev, float momentum,
+                                       int write_back_clipped, float* x2, long n2, const float* void_flag_dev, void* stream);
 int lv_adam_step_f32(float* p, float* g, float* m, float* v, long n, const float* lr_dev, const float* coef_dev,
                      const float* step_dev, float beta1, float beta2, float eps, int write_back_clipped, void* stream);
 /* lv_adam_step_f32 behind the transaction gate (the fused text trainer's optimizer="adam"): torch.optim.Adam (amsgrad=False,

@@ -70,6 +70,9 @@ SIGNATURES = {
     "lv_sgd_step_txn_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp, _vp],
     "lv_scale_txn_f32": [_vp, _l, _vp, _vp, _vp],
     "lv_sgd_step_scale_txn_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _vp],
+    "lv_sgd_momentum_step_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp],
+    "lv_sgd_momentum_step_txn_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp, _vp],
+    "lv_sgd_momentum_step_scale_txn_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp, _l, _vp, _vp],
     "lv_rng_noise_step": [_vp, _l, _vp, _l, _f, _vp, _l, _f, _vp, _u64, _vp],
     "lv_lstm_persist16_wpk_floats": [],
     "lv_lstm_persist16_xch_floats": [],

@@ -1,4 +1,4 @@
-// lv_optim.hip -- global grad-norm, clip coefficient, fused clip+SGD / clip+Adam over flat parameter buffers.
+// lv_optim.hip -- global grad-norm, clip coefficient, fused clip+SGD (plain and with momentum) / clip+Adam over flat parameter buffers.
 //
 // Replaces torch.nn.utils.clip_grad_norm_(vae.parameters(), 5.0) (text.py:385, image.py:312; the norm spans
 // encoder AND decoder grads -- SURVEY.md G1), optim.SGD(lr=1.0, momentum=0).step (text.py:325,387) and
@@ -231,6 +231,72 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
             p[i] -= a * gv;
             if (wb) g[i] = gv;
         }
+    }
+}
+
+// buf * mu + g as torch.optim.SGD forms it -- buf.mul_(momentum).add_(grad): the product is rounded, then the sum (two roundings,
+// never one fused multiply-add).  hipcc contracts a * b + c by default, and this ROCm's __fmul_rn / __fadd_rn are plain * and + that
+// contract just the same: what keeps the two operations apart is the contraction pragma below (checked in the gfx950 ISA under
+// hipcc's default flags: v_mul_f32, v_add_f32) on top of the -ffp-contract=off every build recipe of this library passes; the
+// emulator's g++ has no such pragma and rests on that flag alone (tests/emu/build_emu.py).
+__device__ __forceinline__ float sgd_velocity(float buf, float mu, float g) {
+#pragma clang fp contract(off)
+    const float t = buf * mu;
+    return t + g;
+}
+
+// One element of torch.optim.SGD(momentum=mu, dampening=0, nesterov=False, weight_decay=0) on the clipped gradient c * g:
+// buf <- buf * mu + g'; p <- p - lr * buf, the latter as ONE rounding (torch's add_(buf, alpha=-lr) is a fused multiply-add)
+__device__ __forceinline__ void sgd_momentum_elem(float& p, float& g, float& buf, float c, float mu, float neg_lr) {
+    g = g * c;
+    buf = sgd_velocity(buf, mu, g);
+    p = fmaf(neg_lr, buf, p);
+}
+
+// The momentum twin of sgd_kernel (lv_sgd_momentum_step*_f32): one velocity element per parameter element, laid out like p.
+// A zero velocity buffer is torch's "no momentum_buffer yet" (0 * mu + g' = g' bit for bit), so there is no step counter.
+// A no-op while the transaction gate's void flag is up: p, g, buf and x2 keep their bit patterns.
+__global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, long n,
+                                                           const float* __restrict__ lr, const float* __restrict__ coef, float mu,
+                                                           int write_back, const float* __restrict__ void_flag,
+                                                           float* __restrict__ x2, long n2) {
+    if (void_flag && void_flag[0] != 0.f) return;
+    const float c = coef ? coef[0] : 1.f;
+    const long stride = (long)gridDim.x * 256;
+    const long tid0 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (x2 && c != 1.0f) {
+        const long m4 = (((uintptr_t)x2) & 15) == 0 ? n2 / 4 : 0;
+        float4* x4 = reinterpret_cast<float4*>(x2);
+        for (long i = tid0; i < m4; i += stride) {
+            float4 v = x4[i];
+            v.x *= c; v.y *= c; v.z *= c; v.w *= c;
+            x4[i] = v;
+        }
+        for (long i = m4 * 4 + tid0; i < n2; i += stride) x2[i] *= c;
+    }
+    const float na = -lr[0];
+    const bool wb = write_back && c != 1.0f;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf)) & 15) == 0;
+    const long n4 = vec ? n / 4 : 0;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+    for (long i = tid0; i < n4; i += stride) {
+        float4 pv = p4[i], gv = g4[i], bv = b4[i];
+        sgd_momentum_elem(pv.x, gv.x, bv.x, c, mu, na);
+        sgd_momentum_elem(pv.y, gv.y, bv.y, c, mu, na);
+        sgd_momentum_elem(pv.z, gv.z, bv.z, c, mu, na);
+        sgd_momentum_elem(pv.w, gv.w, bv.w, c, mu, na);
+        p4[i] = pv;
+        b4[i] = bv;
+        if (wb) g4[i] = gv;
+    }
+    for (long i = n4 * 4 + tid0; i < n; i += stride) {
+        float pv = p[i], gv = g[i], bv = buf[i];
+        sgd_momentum_elem(pv, gv, bv, c, mu, na);
+        p[i] = pv;
+        buf[i] = bv;
+        if (wb) g[i] = gv;
     }
 }
 
@@ -518,6 +584,38 @@ extern "C" int lv_sgd_step_scale_txn_f32(float* p, float* g, long n, const float
               void_flag_dev, x2, n2);
     LV_CHECK_LAUNCH();
     return LV_OK;
+}
+
+// torch.optim.SGD(momentum > 0) (text.py --momentum: text.py:30,325-326) over a flat buffer: buf <- buf * momentum + coef * g,
+// p <- p - lr * buf, bit for bit torch's arithmetic (see sgd_momentum_elem).  x2 / n2: see lv_sgd_step_scale_txn_f32.
+static int sgd_momentum_step(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev, float momentum,
+                             int write_back_clipped, float* x2, long n2, const float* void_flag_dev, void* stream) {
+    if (n == 0 && n2 == 0) return LV_OK;
+    LV_LAUNCH(sgd_momentum_kernel, dim3(lv_stream_grid(n > n2 ? n : n2)), dim3(256), 0, stream, p, g, buf, n, lr_dev, coef_dev, momentum,
+              write_back_clipped, void_flag_dev, x2, n2);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+extern "C" int lv_sgd_momentum_step_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev,
+                                        float momentum, int write_back_clipped, void* stream) {
+    if (!p || !g || !buf || !lr_dev || n < 0) return LV_ERR_ARG;
+    return sgd_momentum_step(p, g, buf, n, lr_dev, coef_dev, momentum, write_back_clipped, nullptr, 0, nullptr, stream);
+}
+
+// lv_sgd_momentum_step_f32 behind the transaction gate: p, g and buf stay untouched while void_flag_dev[0] != 0
+extern "C" int lv_sgd_momentum_step_txn_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev,
+                                            float momentum, int write_back_clipped, const float* void_flag_dev, void* stream) {
+    if (!p || !g || !buf || !lr_dev || !void_flag_dev || n < 0) return LV_ERR_ARG;
+    return sgd_momentum_step(p, g, buf, n, lr_dev, coef_dev, momentum, write_back_clipped, nullptr, 0, void_flag_dev, stream);
+}
+
+// lv_sgd_momentum_step_txn_f32 on (p, g, buf) + lv_scale_txn_f32 on x2 (the gradient of the side that is not stepped) in one launch
+extern "C" int lv_sgd_momentum_step_scale_txn_f32(float* p, float* g, float* buf, long n, const float* lr_dev, const float* coef_dev,
+                                                  float momentum, int write_back_clipped, float* x2, long n2,
+                                                  const float* void_flag_dev, void* stream) {
+    if (!p || !g || !buf || !lr_dev || !coef_dev || !void_flag_dev || !x2 || n < 0 || n2 < 0) return LV_ERR_ARG;
+    return sgd_momentum_step(p, g, buf, n, lr_dev, coef_dev, momentum, write_back_clipped, x2, n2, void_flag_dev, stream);
 }
 
 extern "C" int lv_scale_txn_f32(float* x, long n, const float* coef_dev, const float* void_flag_dev, void* stream) {

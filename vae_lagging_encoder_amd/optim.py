@@ -11,8 +11,9 @@ two lines, same call shape and semantics as torch's, running over those flat buf
     lvae_optim.clip_grad_norm_(vae.parameters(), clip_grad)                  # text.py:385: norm over encoder AND decoder gradients
     enc_optimizer.step()                                                     # text.py:387
 
-Wherever the gradients are NOT the flat views (another model, gradient accumulation, a parameter the engines do not own) both fall
-back to torch's own implementation on the tensors they were given -- same result, more launches.
+SGD with momentum (text.py --momentum) takes the same route, with one flat velocity tensor per module.  Wherever the gradients are NOT
+the flat views (another model, gradient accumulation, a parameter the engines do not own) both fall back to torch's own
+implementation on the tensors they were given -- same result, more launches.
 """
 import torch
 
@@ -78,25 +79,51 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
 
 
 class SGD(torch.optim.SGD):
-    """optim.SGD(params, lr, momentum=0) of text.py:325-326 -- `p -= lr * p.grad` -- as one streaming launch over a module's flat
-    buffers when the parameters are exactly one engine's and their gradients the flat views; anything else (momentum, weight decay,
-    foreign parameters) is torch's own step.  `param_groups[0]["lr"]` is read at every step, as the reference's lr decay writes it
-    (text.py:470-480 rebuilds the optimizer; schedulers that edit the group work too)."""
+    """optim.SGD(params, lr, momentum) of text.py:325-326 as one streaming launch over a module's flat buffers when the parameters
+    are exactly one engine's and their gradients the flat views: `p -= lr * p.grad` for momentum 0, and for momentum > 0 (text.py
+    --momentum; dampening 0, no nesterov) `buf = buf * momentum + p.grad; p -= lr * buf` with torch's own roundings
+    (lv_sgd_momentum_step_f32).  The velocity is then one flat tensor per engine, and `state[p]["momentum_buffer"]` are views into
+    it at the parameter's offset and shape, so state_dict() has torch's layout; a momentum_buffer that is not such a view
+    (load_state_dict) is copied into the flat tensor once.  Anything else (weight decay, nesterov, dampening, several groups,
+    foreign parameters) is torch's own step.  `param_groups[0]["lr"]` is read at every step, as the reference's lr decay writes
+    it (text.py:470-480 rebuilds the optimizer; schedulers that edit the group work too)."""
 
     def __init__(self, params, lr=1.0, **kw):
         super().__init__(params, lr=lr, **kw)
         self._lr_dev = {}
+        self._flat_buf = {}            # id(FlatBuffer) -> (the FlatBuffer, its flat velocity tensor) (momentum > 0)
+
+    def _velocity(self, f):
+        """The flat velocity of flat buffer f, with every parameter's momentum_buffer a view into it."""
+        ent = self._flat_buf.get(id(f))
+        # (the entry keeps f alive, so its id cannot be recycled; a flat buffer whose storage was rebuilt gets a new velocity, filled
+        # from the parameters' momentum_buffer below)
+        if ent is None or ent[0] is not f or ent[1].shape != f.data.shape or ent[1].device != f.data.device:
+            ent = self._flat_buf[id(f)] = (f, torch.zeros_like(f.data))
+        buf = ent[1]
+        for n, p in zip(f.names, f.params):
+            o = f.offsets[n]
+            view = buf[o:o + p.numel()].view(p.shape)
+            st = self.state[p]
+            cur = st.get("momentum_buffer")
+            if cur is not None and cur.data_ptr() == view.data_ptr() and cur.shape == view.shape:
+                continue
+            if cur is not None:
+                view.copy_(cur)            # a foreign buffer (load_state_dict, an earlier torch step): taken over once
+            st["momentum_buffer"] = view
+        return buf
 
     @torch.no_grad()
     def step(self, closure=None):
-        plain = all(g["momentum"] == 0 and g["weight_decay"] == 0 and g["dampening"] == 0 and not g["nesterov"] and not g.get("maximize", False)
-                    for g in self.param_groups)
-        if closure is not None or not plain or len(self.param_groups) != 1:
+        simple = all(g["momentum"] >= 0 and g["weight_decay"] == 0 and g["dampening"] == 0 and not g["nesterov"] and not g.get("maximize", False)
+                     for g in self.param_groups)
+        if closure is not None or not simple or len(self.param_groups) != 1:
             return super().step(closure)
         group = self.param_groups[0]
         flats = _owner_flats([p for p in group["params"] if p.grad is not None])
         if not flats or sum(len(f.params) for f in flats) != len(group["params"]):
             return super().step()
+        mu = float(group["momentum"])
         for f in flats:
             dev = f.device
             lib, s = _eng.backend_for(dev), _eng.stream_ptr(dev)
@@ -105,6 +132,10 @@ class SGD(torch.optim.SGD):
             if t is None:
                 self._lr_dev = {key: torch.tensor([float(group["lr"]), 1.0], dtype=torch.float32, device=dev)}
                 t = self._lr_dev[key]
-            lib.lv_sgd_step_f32(P(f.data), P(f.grad), f.numel, P(t, 0), P(t, 1), 0, s)       # coef 1: the clip already scaled the gradient
+            # coef 1: the clip already scaled the gradient
+            if mu == 0:
+                lib.lv_sgd_step_f32(P(f.data), P(f.grad), f.numel, P(t, 0), P(t, 1), 0, s)
+            else:
+                lib.lv_sgd_momentum_step_f32(P(f.data), P(f.grad), P(self._velocity(f)), f.numel, P(t, 0), P(t, 1), mu, 0, s)
             f.params[0]._lvae_engine.wgen += 1        # a raw-pointer update is invisible to torch's version counters (engine.weights_version)
         return None

@@ -68,13 +68,19 @@ class AggressiveTextTrainer(object):
 
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
                  precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1):
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0):
         """nsamples = ns > 1: text.py --nsamples, VAE.loss(x, kl_weight, nsamples=ns) (vae.py:79-98) -- ns reparameterised samples per
         sentence, the decoder on B * ns rows (row b * ns + s), the reconstruction term averaged over the samples; the report sums stay
         sums over the B sentences.  Noise shapes: eps [B][ns][nz], mask_in [B][T-1][ni] (dropout_in acts before the expansion: one mask
         per sentence), mask_out [B*ns][T-1][H].  The word half of the decoder's input projection and its backward run once per
         sentence (engine.LSTMDecoderEngine.forward).  Single GPU, eager mode, one micro-batch, decoder_grads = "full".
-        optimizer = "sgd" (default: optim.SGD(momentum=0), text.py:325-326) or "adam": torch.optim.Adam(lr, betas, eps) on each of
+        momentum = mu > 0 (optimizer "sgd" only): text.py --momentum, optim.SGD(lr, momentum=mu) on both sides (text.py:30,325-326) --
+        one velocity buffer per flat parameter buffer (`sgd_buf`, laid out like flat.data: a parameter's velocity sits at
+        flat.offsets[name]), updated by lv_sgd_momentum_step_txn_f32 behind the transaction gate with torch's own roundings (a
+        voided step moves neither weights nor velocity; only the stepped side's velocity moves); reset_optimizer() zeroes both
+        (text.py:492-493).  mu = 0 allocates nothing and issues the plain SGD launches.  Works with grad_sync, micro_batches,
+        use_graph, nsamples and fold_norm: the step consumes whatever gradient they leave in flat.grad.
+        optimizer = "sgd" (default: optim.SGD(lr, momentum), text.py:325-326) or "adam": torch.optim.Adam(lr, betas, eps) on each of
         the two sides, as toy.py --optim adam builds them (toy.py:289-290) -- first and second moments per flat buffer, one step
         count per optimizer in device memory, all behind the transaction gate (lv_adam_step_txn_f32: a voided step moves none of
         them).  `lr` is the learning rate of either optimizer; reset_optimizer() re-creates them (toy.py:506-511).  Single GPU,
@@ -105,6 +111,11 @@ class AggressiveTextTrainer(object):
             raise ValueError("optimizer='adam' runs on a single GPU with micro_batches = 1 (no grad_sync): the Adam step is not "
                              "implemented for data parallelism or gradient accumulation")
         self.optimizer = optimizer
+        self.momentum = float(momentum)
+        if self.momentum < 0:
+            raise ValueError("momentum must be >= 0, not %r" % (momentum,))
+        if self.momentum != 0 and optimizer != "sgd":
+            raise ValueError("momentum = %r is optim.SGD's: optimizer='adam' has its betas" % (momentum,))
         self.nsamples = int(nsamples)
         if self.nsamples < 1:
             raise ValueError("nsamples must be >= 1, not %r" % (nsamples,))
@@ -168,6 +179,10 @@ class AggressiveTextTrainer(object):
         if optimizer == "adam":
             self.adam_m = {"enc": torch.zeros_like(self.enc.flat.data), "dec": torch.zeros_like(self.dec.flat.data)}
             self.adam_v = {"enc": torch.zeros_like(self.enc.flat.data), "dec": torch.zeros_like(self.dec.flat.data)}
+        # optim.SGD(momentum > 0): the two velocity buffers (None with momentum off: the plain SGD launches, nothing allocated)
+        self.sgd_buf = None
+        if self.momentum != 0:
+            self.sgd_buf = {"enc": torch.zeros_like(self.enc.flat.data), "dec": torch.zeros_like(self.dec.flat.data)}
         self._klw_host = 0.0                  # host copy of scal[0]
         self._journal = []                    # steps queued since the last host check: (x, kl_weight, noise, update)
         self._committed_base = 0.0            # scal[9] at the last host check
@@ -197,11 +212,15 @@ class AggressiveTextTrainer(object):
     ADAM_STEP = {"enc": 13, "dec": 14}          # scal slots of the two step counts
 
     def reset_optimizer(self, lr, betas=None):
-        """Re-create both optimizers with learning rate `lr` (toy.py:506-511 after a decay): SGD has no state; Adam's first and
+        """Re-create both optimizers with learning rate `lr` (toy.py:506-511, text.py:492-493 after a decay): plain SGD has no
+        state; SGD with momentum starts from zero velocities again (in place: captured graphs stay valid); Adam's first and
         second moments and both step counts start from zero again, with `betas` (None keeps the current ones).  Everything
         queued before is applied first (one host read)."""
         self.commit()
         self.scal[1] = lr
+        if self.sgd_buf is not None:
+            for k in ("enc", "dec"):
+                self.sgd_buf[k].zero_()
         if self.optimizer != "adam":
             return
         if betas is not None and (float(betas[0]), float(betas[1])) != self.betas:
@@ -471,6 +490,8 @@ class AggressiveTextTrainer(object):
         # clip_grad_norm_ scales every grad in place; the update only touches the stepped side; both are no-ops under the void flag
         if self.optimizer == "adam":
             self._adam_step(update, ef, df)
+        elif self.sgd_buf is not None:
+            self._sgd_momentum_step(update, ef, df)
         elif update == "both":
             lib.lv_sgd_step_txn_f32(P(ef.data), P(ef.grad), ef.numel, self._s(1), self._s(3), 1, self._s(8), s)
             lib.lv_sgd_step_txn_f32(P(df.data), P(df.grad), df.numel, self._s(1), self._s(3), 1, self._s(8), s)
@@ -480,6 +501,25 @@ class AggressiveTextTrainer(object):
             if update == "encoder" and self._fold is not None and self.decoder_grads == "norm":
                 b_off, b_n = self._fold.dec_off, self._fold.dec_end - self._fold.dec_off      # what of the decoder's gradient exists
             lib.lv_sgd_step_scale_txn_f32(P(a.data), P(a.grad), a.numel, self._s(1), self._s(3), 1, P(b.grad, b_off), b_n, self._s(8), s)
+
+    def _sgd_momentum_step(self, update, ef, df):
+        """The momentum twin of the SGD update above: lv_sgd_momentum_step_txn_f32 per stepped side (its velocity alone moves), the
+        other side's gradient scaled by the clip coefficient in the same launch; every launch is gated by the void flag."""
+        lib, s = self.lib, _eng.stream_ptr(self.device)
+        sides = {"enc": ef, "dec": df}
+
+        def args(k):
+            f = sides[k]
+            return (P(f.data), P(f.grad), P(self.sgd_buf[k]), f.numel, self._s(1), self._s(3), self.momentum, 1)
+        if update == "both":
+            lib.lv_sgd_momentum_step_txn_f32(*args("enc"), self._s(8), s)
+            lib.lv_sgd_momentum_step_txn_f32(*args("dec"), self._s(8), s)
+            return
+        a, b = ("enc", df) if update == "encoder" else ("dec", ef)
+        b_off, b_n = 0, b.numel
+        if update == "encoder" and self._fold is not None and self.decoder_grads == "norm":
+            b_off, b_n = self._fold.dec_off, self._fold.dec_end - self._fold.dec_off
+        lib.lv_sgd_momentum_step_scale_txn_f32(*args(a), P(b.grad, b_off), b_n, self._s(8), s)
 
     def _adam_step(self, update, ef, df):
         """The Adam twin of the SGD update above: lv_adam_step_txn_f32 per stepped side, the other side's gradient scaled by the

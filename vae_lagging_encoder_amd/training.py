@@ -52,27 +52,28 @@ def guarded_eval(vae, fn, log=print):
 
 class TextTrainingLoop(object):
     """args fields read (text.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
-    iw_nsamples, momentum (must be 0: the fused step is plain SGD, the reference default)."""
+    iw_nsamples, momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...))."""
 
     def __init__(self, vae, train_batches, val_batches, test_batches, args, n_train_sentences=None, trainer=None,
                  log=print, np_rng=None, seed=783435, noise_fn=None, epoch_hook=None):
         """noise_fn(x) -> (eps, mask_in, mask_out): injects the random draws of every training step (parity replays of a
         recorded reference run, tests/test_policy_replay.py); None draws them on the device.  With args.nsamples = ns > 1
         (text.py --nsamples) in the multi-sample shapes: eps [B][ns][nz], mask_in [B][T-1][ni], mask_out [B*ns][T-1][H].
-        A `trainer` that is handed in must have been built with the same nsamples.
+        A `trainer` that is handed in must have been built with the same nsamples and the same momentum as args'.
         epoch_hook(loop, epoch): called at the top of every epoch, before its batch permutation is drawn (checkpoint / resume
         policies; the replay test re-synchronises the weights there)."""
         self.vae, self.args, self.log = vae, args, log
         self.noise_fn = noise_fn
         self.epoch_hook = epoch_hook
         self.train_batches, self.val_batches, self.test_batches = train_batches, val_batches, test_batches
-        if getattr(args, "momentum", 0) != 0:
-            raise ValueError("the fused driver implements optim.SGD(momentum=0), the reference's default (text.py:325-326)")
+        self.momentum = float(getattr(args, "momentum", 0))
+        if trainer is not None and float(getattr(trainer, "momentum", 0.0)) != self.momentum:
+            raise ValueError("args.momentum = %r, but the trainer was built with momentum = %r" % (self.momentum, getattr(trainer, "momentum", 0.0)))
         self.nsamples = int(getattr(args, "nsamples", 1))
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
         self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
-                                                                                 nsamples=self.nsamples)
+                                                                                 nsamples=self.nsamples, momentum=self.momentum)
         if hasattr(self.trainer, "prepare_batches"):
             self.trainer.prepare_batches(train_batches)          # per-batch index structures, built once with the batch list
         self.rng = np_rng if np_rng is not None else np.random
@@ -125,7 +126,7 @@ class TextTrainingLoop(object):
                     self.vae.load_state_dict(self.best["state"])
                 self.log("new lr: %f" % self.opt["lr"])
                 self.decay_cnt += 1
-                self.trainer.set_lr(self.opt["lr"])
+                self.trainer.reset_optimizer(self.opt["lr"])          # text.py:492-493: new optimizers (momentum: zero velocities)
         else:
             self.opt["not_improved"] = 0
             self.opt["best_loss"] = loss
