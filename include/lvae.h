@@ -118,6 +118,12 @@ int lv_cvt_bf16_f32(const float* src, long lds, int R, int C, uint16_t* dst, lon
  * backward on dO, in place.  (The persistent recurrences then run without a mask: +0.3 us per timestep otherwise.) */
 int lv_cvt_bf16_keep_f32(const float* src, long lds, int T, int Bsz, int C, const uint8_t* keep, float kscale,
                          uint16_t* dst, long ldd, uint16_t* dstT, long ldt, void* stream);
+/* The decoder's three images of its hidden states in ONE pass: src = hs [(T + 1) * Bsz][C] time-major with the initial state in
+ * front (row t*Bsz + b = h_{t-1}[b]).  hT [C][T*Bsz](ldh) = the transposed image of rows [0, T*Bsz) (h_{t-1}: the operand of dW_hh),
+ * exactly lv_cvt_bf16_f32's; dst [T*Bsz][C](ldd) / dstT [C][T*Bsz](ldt) = the images of rows [Bsz, (T + 1)*Bsz) (h_t, the LSTM output),
+ * exactly lv_cvt_bf16_keep_f32's with (keep, kscale), or lv_cvt_bf16_f32's when keep is NULL.  All three are required. */
+int lv_cvt_bf16_hs3_f32(const float* src, long lds, int T, int Bsz, int C, const uint8_t* keep, float kscale, uint16_t* dst, long ldd,
+                        uint16_t* dstT, long ldt, uint16_t* hT, long ldh, void* stream);
 /* dst f32 [n] = bf16 src [n] * scale: unpacks a bf16 gradient payload of the data-parallel exchange (dist.GradSync payload="bf16") */
 int lv_cvt_f32_bf16_scaled(const uint16_t* src, long n, float scale, float* dst, void* stream);
 int lv_keep_scale_f32(float* x, const uint8_t* keep, float kscale, int T, int Bsz, int C, void* stream);
@@ -395,6 +401,14 @@ int lv_scale_txn_f32(float* x, long n, const float* coef_dev, const float* void_
  * clip_grad_norm_ (text.py:385) scales all the same -- in one launch */
 int lv_sgd_step_scale_txn_f32(float* p, float* g, long n, const float* lr_dev, const float* coef_dev, int write_back_clipped,
                               float* x2, long n2, const float* void_flag_dev, void* stream);
+/* The same step where elements [emb_off, emb_off + V * ni) of (p, g) are an embedding table whose gradient was written THIS step by
+ * lv_embed_scatter_full* from the sorted token list sorted_tok[0 .. N) (tokens in [0, V)) and not added to since: every row no token
+ * names holds +0, so p - lr * coef * 0 leaves it as it is and the launch neither reads nor writes it.  Results equal
+ * lv_sgd_step_scale_txn_f32 bit for bit (void flag and write_back_clipped included); when lr or the coefficient read from the
+ * device is negative, inf or NaN -- where a zero gradient does move p -- the launch walks every row like the dense entry. */
+int lv_sgd_step_scale_rows_txn_f32(float* p, float* g, long n, const float* lr_dev, const float* coef_dev, int write_back_clipped,
+                                   float* x2, long n2, const float* void_flag_dev, long emb_off, int V, int ni, const int* sorted_tok,
+                                   int N, void* stream);
 /* torch.optim.SGD(lr, momentum) with momentum > 0 (text.py --momentum: text.py:30, 325-326, re-created after a decay at 492-493;
  * dampening 0, no nesterov, no weight decay) over a flat buffer, one velocity element per parameter element in `buf`:
  *     g' = g * coef;  buf = round(round(buf * momentum) + g');  p = fma(-lr, buf, p)

@@ -41,6 +41,7 @@ SIGNATURES = {
     "lv_softmax_nll_bwd_h16": [_vp, _l, _vp, _vp, _l, _i, _vp, _vp, _l, _i, _i, _i, _vp],
     "lv_cvt_bf16_f32": [_vp, _l, _i, _i, _vp, _l, _vp, _l, _vp],
     "lv_cvt_bf16_keep_f32": [_vp, _l, _i, _i, _i, _vp, _f, _vp, _l, _vp, _l, _vp],
+    "lv_cvt_bf16_hs3_f32": [_vp, _l, _i, _i, _i, _vp, _f, _vp, _l, _vp, _l, _vp, _l, _vp],
     "lv_cvt_f32_bf16_scaled": [_vp, _l, _f, _vp, _vp],
     "lv_keep_scale_f32": [_vp, _vp, _f, _i, _i, _i, _vp],
     "lv_cvt_bf16_gates_f32": [_vp, _l, _i, _i, _vp, _l, _vp, _l, _vp],
@@ -70,6 +71,7 @@ SIGNATURES = {
     "lv_sgd_step_txn_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp, _vp],
     "lv_scale_txn_f32": [_vp, _l, _vp, _vp, _vp],
     "lv_sgd_step_scale_txn_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _vp],
+    "lv_sgd_step_scale_rows_txn_f32": [_vp, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _i, _i, _vp, _i, _vp],
     "lv_sgd_momentum_step_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp],
     "lv_sgd_momentum_step_txn_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp, _vp],
     "lv_sgd_momentum_step_scale_txn_f32": [_vp, _vp, _vp, _l, _vp, _vp, _f, _i, _vp, _l, _vp, _vp],

@@ -1995,6 +1995,100 @@ __global__ __launch_bounds__(256) void cvt_b16_v4_kernel(const float* __restrict
     }
 }
 
+// The decoder's hidden states hs [(T + 1) * Bsz][C] (row t*Bsz + b = h_{t-1}[b], the initial state in front) feed two conversions:
+// rows [Bsz, (T + 1) Bsz) -- h_t, the LSTM output -- as O and O^T with dropout_out folded in (the keep form above), and rows
+// [0, T Bsz) -- h_{t-1} -- as the transposed operand of dW_hh.  This kernel reads every row ONCE (cvt_b16_v4_kernel's access
+// pattern: a float4 and a 4-byte mask word per lane and row, 8-byte stores) and writes all three images; a 64-row tile of src holds
+// columns [r0, r0 + 64) of hT and columns [r0 - Bsz, r0 - Bsz + 64) of dstT.  The arithmetic per element is that of the two
+// separate launches, so the images are the same bits.  The mask belongs to the OUTPUT row: source row q >= Bsz is output row
+// q - Bsz = (t - 1) Bsz + b.  dstT leaves as 8-byte stores where Bsz % 4 == 0 keeps its shifted columns aligned, else as 2-byte ones.
+__global__ __launch_bounds__(256) void cvt_b16_hs3_kernel(const float* __restrict__ src, long lds_, int T, int Bsz, int C,
+                                                          const uint8_t* __restrict__ keep, float kscale,
+                                                          uint16_t* __restrict__ dst, long ldd, uint16_t* __restrict__ dstT, long ldt,
+                                                          uint16_t* __restrict__ hT, long ldh) {
+    __shared__ __attribute__((aligned(8))) uint16_t tile[2][64][68];      // [0] plain (h_{t-1}), [1] with the keep mask (output)
+    const int t = (int)threadIdx.x;
+    const int r0 = (int)blockIdx.y * 64, c0 = (int)blockIdx.x * 64;
+    const int q = t >> 4, cl = t & 15;
+    const int RO = T * Bsz, R = RO + Bsz;
+    const int ko = keep ? 1 : 0;
+    int bb = (r0 + q) % Bsz, tt = (r0 + q) / Bsz;
+    const int gc = c0 + 4 * cl;
+    const int gcc = gc < C ? gc : C - 4;
+    int grs[4], bbs[4], tts[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        grs[u] = r0 + q + 16 * u;
+        bbs[u] = bb; tts[u] = tt;
+        bb += 16;
+        while (bb >= Bsz) { bb -= Bsz; ++tt; }
+    }
+    float4 v[4];
+    uint32_t kp[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(src + (long)(grs[u] < R ? grs[u] : R - 1) * lds_ + gcc);
+    if (keep) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool out_row = grs[u] < R && tts[u] >= 1;                // (clamped to the mask's first row otherwise: never used)
+            kp[u] = *reinterpret_cast<const uint32_t*>(keep + ((long)(out_row ? bbs[u] : 0) * T + (out_row ? tts[u] - 1 : 0)) * C + gcc);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int gr = grs[u];
+        uint16_t b[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
+        if (gr < R && gc < C) {
+            const float xs[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float x = xs[e];
+                b[e] = (uint16_t)lv_f32_to_bf16_bits(x);
+                if (keep) {
+                    x *= ((kp[u] >> (8 * e)) & 0xFFu) ? kscale : 0.f;      // as h * (keep * scale) rounds (a dropped negative element is -0)
+                    d[e] = (uint16_t)lv_f32_to_bf16_bits(x);
+                } else d[e] = b[e];
+            }
+            if (gr >= Bsz)
+                *reinterpret_cast<uint2*>(dst + (long)(gr - Bsz) * ldd + gc) = make_uint2((uint32_t)d[0] | ((uint32_t)d[1] << 16), (uint32_t)d[2] | ((uint32_t)d[3] << 16));
+        }
+        *reinterpret_cast<uint2*>(&tile[0][q + 16 * u][4 * cl]) = make_uint2((uint32_t)b[0] | ((uint32_t)b[1] << 16), (uint32_t)b[2] | ((uint32_t)b[3] << 16));
+        if (keep)
+            *reinterpret_cast<uint2*>(&tile[1][q + 16 * u][4 * cl]) = make_uint2((uint32_t)d[0] | ((uint32_t)d[1] << 16), (uint32_t)d[2] | ((uint32_t)d[3] << 16));
+    }
+    __syncthreads();
+    // transposed images: lane (column-in-pass t >> 4, row quad t & 15) stores source rows 4 rl .. 4 rl + 3 of column c
+    const int rl = t & 15, gr = r0 + 4 * rl;
+    const bool otv = (Bsz & 3) == 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = q + 16 * i, gct = c0 + c;
+        if (gct >= C) continue;
+        {
+            const uint16_t e0 = tile[0][4 * rl][c], e1 = tile[0][4 * rl + 1][c], e2 = tile[0][4 * rl + 2][c], e3 = tile[0][4 * rl + 3][c];
+            uint16_t* o = hT + (long)gct * ldh + gr;
+            if (gr + 3 < RO) *reinterpret_cast<uint2*>(o) = make_uint2((uint32_t)e0 | ((uint32_t)e1 << 16), (uint32_t)e2 | ((uint32_t)e3 << 16));
+            else {
+                if (gr < RO) o[0] = e0;
+                if (gr + 1 < RO) o[1] = e1;
+                if (gr + 2 < RO) o[2] = e2;
+            }
+        }
+        {
+            const uint16_t e0 = tile[ko][4 * rl][c], e1 = tile[ko][4 * rl + 1][c], e2 = tile[ko][4 * rl + 2][c], e3 = tile[ko][4 * rl + 3][c];
+            uint16_t* orow = dstT + (long)gct * ldt;
+            if (otv && gr >= Bsz && gr + 3 < R)
+                *reinterpret_cast<uint2*>(orow + (gr - Bsz)) = make_uint2((uint32_t)e0 | ((uint32_t)e1 << 16), (uint32_t)e2 | ((uint32_t)e3 << 16));
+            else {
+                if (gr >= Bsz && gr < R) orow[gr - Bsz] = e0;
+                if (gr + 1 >= Bsz && gr + 1 < R) orow[gr + 1 - Bsz] = e1;
+                if (gr + 2 >= Bsz && gr + 2 < R) orow[gr + 2 - Bsz] = e2;
+                if (gr + 3 >= Bsz && gr + 3 < R) orow[gr + 3 - Bsz] = e3;
+            }
+        }
+    }
+}
+
 // picks the 16-byte form where the operands allow it
 static void cvt_launch(void* stream, const float* src, long lds, int R, int C, uint16_t* dst, long ldd, uint16_t* dstT, long ldt, int gate_H,
                        const uint8_t* keep, float kscale, int Bsz, const int64_t* gids, long gstride, int gV, int lo) {
@@ -2359,6 +2453,30 @@ extern "C" int lv_cvt_bf16_keep_f32(const float* src, long lds, int T, int Bsz, 
     if (R == 0 || C == 0) return LV_OK;
     cvt_launch(stream, src, lds, (int)R, C,
               dst, ldd, dstT, ldt, 0, keep, kscale, Bsz, (const int64_t*)nullptr, 0L, 0, 0);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// All three images of the decoder's hidden states from one read of hs (see cvt_b16_hs3_kernel): src [(T + 1) * Bsz][C]; hT [C][T*Bsz]
+// = lv_cvt_bf16_f32's transposed image of rows [0, T*Bsz); dst [T*Bsz][C] / dstT [C][T*Bsz] = lv_cvt_bf16_keep_f32's images (keep NULL:
+// lv_cvt_bf16_f32's) of rows [Bsz, (T + 1) * Bsz).  Where the operands do not allow 16-byte accesses the two separate conversions run.
+extern "C" int lv_cvt_bf16_hs3_f32(const float* src, long lds, int T, int Bsz, int C, const uint8_t* keep, float kscale,
+                                   uint16_t* dst, long ldd, uint16_t* dstT, long ldt, uint16_t* hT, long ldh, void* stream) {
+    if (!src || !dst || !dstT || !hT) return LV_ERR_ARG;
+    const long RO = (long)T * Bsz;
+    if (T < 0 || Bsz <= 0 || C < 0 || lds < C || ldd < C || ldt < RO || ldh < RO || RO + Bsz >= (1L << 31)) return LV_ERR_SHAPE;
+    if (RO == 0 || C == 0) return LV_OK;
+    const bool v4 = C >= 4 && C % 4 == 0 && lds % 4 == 0 && (((uintptr_t)src) & 15) == 0 && ldd % 4 == 0 && (((uintptr_t)dst) & 7) == 0 &&
+                    ldt % 4 == 0 && (((uintptr_t)dstT) & 7) == 0 && ldh % 4 == 0 && (((uintptr_t)hT) & 7) == 0 &&
+                    (!keep || (((uintptr_t)keep) & 3) == 0);
+    if (v4) {
+        const dim3 grid((unsigned)lv_cdiv(C, 64), (unsigned)lv_cdiv(RO + Bsz, 64)), block(256);
+        LV_LAUNCH(cvt_b16_hs3_kernel, grid, block, 0, stream, src, lds, T, Bsz, C, keep, kscale, dst, ldd, dstT, ldt, hT, ldh);
+    } else {
+        cvt_launch(stream, src + (long)Bsz * lds, lds, (int)RO, C, dst, ldd, dstT, ldt, 0, keep, keep ? kscale : 1.f, keep ? Bsz : 1,
+                   (const int64_t*)nullptr, 0L, 0, 0);
+        cvt_launch(stream, src, lds, (int)RO, C, (uint16_t*)nullptr, 0L, hT, ldh, 0, (const uint8_t*)nullptr, 1.f, 1, (const int64_t*)nullptr, 0L, 0, 0);
+    }
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

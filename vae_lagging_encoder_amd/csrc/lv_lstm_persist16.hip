@@ -476,7 +476,9 @@ struct __attribute__((aligned(16))) Bwd16Lds {
     int abort;
 };
 
-template <int RP, bool LOCAL>
+// HAS_EXT: p.dh_ext holds an external gradient of every h_t (the decoder: dO).  Without it (the encoder: only h_T has one, dh_last)
+// there is no dhb block and no load for it -- one load per lane, pair and timestep, 26 MB per launch at the Yahoo shape.
+template <int RP, bool LOCAL, bool HAS_EXT>
 __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
     auto put = [](gran_t* q, gran_t v) { if (LOCAL) lv_xcd_store_u64(q, v); else gran_store(q, v); };
     constexpr int NP = Cfg16<RP>::NP, SBK = Cfg16<RP>::SBB;
@@ -549,19 +551,17 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
                                      ((((l & 15) >> 2) & 1) * 16 + 4 * (l & 3) + (l >> 4)) * 16
                                : reinterpret_cast<char*>(px_g) + ((long)(8 * w) * PMEMBERS + member) * SLOTS * 8 + (4 * (l & 15) + (l >> 4)) * 16;
     float dc_rec[NP], gsum[NP][4];
-    float dhb[NP][SBK], ctb[NP][SBK + 1];
+    float dhb[HAS_EXT ? NP : 1][HAS_EXT ? SBK : 1], ctb[NP][SBK + 1];
     float4 recb[NP][SBK];
 #pragma unroll
     for (int q = 0; q < NP; ++q) { dc_rec[q] = 0.f; gsum[q][0] = gsum[q][1] = gsum[q][2] = gsum[q][3] = 0.f; }
-    const bool has_ext = p.dh_ext != nullptr;
-    const float* const dh_src = has_ext ? p.dh_ext : p.cs;      // (without dh_ext the loads still run, on any mapped [T][B][H]-sized array)
     auto load_block = [&](int t_hi) {
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
 #pragma unroll
             for (int s2 = 0; s2 < SBK; ++s2) {
                 const int t = t_hi - s2 < 0 ? 0 : t_hi - s2;      // unconditional loads from clamped addresses: see the forward's load_slots
-                dhb[q][s2] = dh_src[(long)t * BH + pidx[q]];
+                if constexpr (HAS_EXT) dhb[q][s2] = p.dh_ext[(long)t * BH + pidx[q]];
                 recb[q][s2] = *reinterpret_cast<const float4*>(sv + (long)t * rec + sg[q]);
             }
 #pragma unroll
@@ -813,7 +813,10 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
             for (int q = 0; q < NP; ++q) {
                 float da[4] = {0.f, 0.f, 0.f, 0.f};
                 if (own[q]) {
-                    float dh = (has_ext ? dhb[q][s2] : 0.f) + dh_rec[q];
+                    // (no external gradient: the + 0 stays -- it is what makes a received sum of -0 a +0, as an all-zero dh_ext does)
+                    float dh;
+                    if constexpr (HAS_EXT) dh = dhb[q][s2] + dh_rec[q];
+                    else dh = 0.f + dh_rec[q];
                     if (t == T - 1 && p.dh_last) dh += p.dh_last[pidx[q]];
                     const float ig = recb[q][s2].x, fg = recb[q][s2].y, gg = recb[q][s2].z, og_ = recb[q][s2].w;
                     const float tc = (LV_P16_ABL & 4) ? 0.9f * ctb[q][s2] : lv_tanh_fast(ctb[q][s2]);
@@ -1052,15 +1055,17 @@ extern "C" int lv_lstm_bwd_bf16_persist16(const float* dh_ext, const float* dh_l
     Bwd16P p{dh_ext, dh_last, reinterpret_cast<const uint4*>(wpk), saved, cs, hs, dG16, dGsum, dh0, dc0, tanh_init, gxch, status, T, B, R,
              dbl ? reinterpret_cast<uint4*>(xb + XCH_BWD_OFF[1 - half]) : nullptr, cextent / 16};
     const dim3 grid(PGROUPS * PMEMBERS), block(256);
-    if (flags & 1) {
-        if (R <= 4) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<4, true>), grid, block, 0, stream, p);
-        else if (R <= 8) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<8, true>), grid, block, 0, stream, p);
-        else LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<16, true>), grid, block, 0, stream, p);
-    } else {
-        if (R <= 4) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<4, false>), grid, block, 0, stream, p);
-        else if (R <= 8) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<8, false>), grid, block, 0, stream, p);
-        else LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<16, false>), grid, block, 0, stream, p);
-    }
+    const bool local = (flags & 1) != 0, ext = dh_ext != nullptr;
+#define LV_BWD16_LAUNCH(RP_) do { \
+        if (local && ext) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<RP_, true, true>), grid, block, 0, stream, p); \
+        else if (local) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<RP_, true, false>), grid, block, 0, stream, p); \
+        else if (ext) LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<RP_, false, true>), grid, block, 0, stream, p); \
+        else LV_LAUNCH_RESIDENT((lstm_bwd_persist_rs16_kernel<RP_, false, false>), grid, block, 0, stream, p); \
+    } while (0)
+    if (R <= 4) LV_BWD16_LAUNCH(4);
+    else if (R <= 8) LV_BWD16_LAUNCH(8);
+    else LV_BWD16_LAUNCH(16);
+#undef LV_BWD16_LAUNCH
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

@@ -185,6 +185,48 @@ __global__ void txn_guard_kernel(const int* status1, const int* status2, float* 
         guard[0] = ((status1 && status1[0] != 0) || (status2 && status2[0] != 0)) ? 1.f : 0.f;
 }
 
+// x *= c over [0, n) by workgroup blk of nblk (16-byte accesses where the buffer allows)
+__device__ __forceinline__ void scale_range(float* __restrict__ x2, long n2, float c, long blk, long nblk) {
+    const long stride2 = nblk * 256;
+    const long m4 = (((uintptr_t)x2) & 15) == 0 ? n2 / 4 : 0;
+    float4* x4 = reinterpret_cast<float4*>(x2);
+    for (long i = blk * 256 + threadIdx.x; i < m4; i += stride2) {
+        float4 v = x4[i];
+        v.x *= c; v.y *= c; v.z *= c; v.w *= c;
+        x4[i] = v;
+    }
+    for (long i = m4 * 4 + blk * 256 + threadIdx.x; i < n2; i += stride2) x2[i] *= c;
+}
+
+// g <- g*c (written back when wb); p <- p - a * g over [0, n) by workgroup blk of nblk
+__device__ __forceinline__ void sgd_range(float* __restrict__ p, float* __restrict__ g, long n, float a, float c, bool wb, long blk, long nblk) {
+    const long stride = nblk * 256;
+    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g)) & 15) == 0;
+    if (vec) {
+        const long n4 = n / 4;
+        float4* p4 = reinterpret_cast<float4*>(p);
+        float4* g4 = reinterpret_cast<float4*>(g);
+        for (long i = blk * 256 + threadIdx.x; i < n4; i += stride) {
+            float4 gv = g4[i], pv = p4[i];
+            gv.x *= c; gv.y *= c; gv.z *= c; gv.w *= c;
+            pv.x -= a * gv.x; pv.y -= a * gv.y; pv.z -= a * gv.z; pv.w -= a * gv.w;
+            p4[i] = pv;
+            if (wb) g4[i] = gv;
+        }
+        for (long i = n4 * 4 + blk * 256 + threadIdx.x; i < n; i += stride) {
+            const float gv = g[i] * c;
+            p[i] -= a * gv;
+            if (wb) g[i] = gv;
+        }
+    } else {
+        for (long i = blk * 256 + threadIdx.x; i < n; i += stride) {
+            const float gv = g[i] * c;
+            p[i] -= a * gv;
+            if (wb) g[i] = gv;
+        }
+    }
+}
+
 // g <- g*coef (optional write-back); p <- p - lr * g
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ g, long n,
                                                   const float* __restrict__ lr, const float* __restrict__ coef,
@@ -192,44 +234,64 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
                                                   float* __restrict__ x2, long n2) {
     if (void_flag && void_flag[0] != 0.f) return;      // the step was voided by the transaction gate: nothing is applied
     const float c = coef ? coef[0] : 1.f;
-    if (x2 && c != 1.0f) {
-        // clip_grad_norm_ scales EVERY gradient, the buffer that is not stepped too: in this launch instead of one of its own
-        // (16-byte accesses where the buffer allows: 150 MB of decoder gradient at the Yahoo shape whenever the clip is active)
-        const long stride2 = (long)gridDim.x * 256;
-        const long m4 = (((uintptr_t)x2) & 15) == 0 ? n2 / 4 : 0;
-        float4* x4 = reinterpret_cast<float4*>(x2);
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m4; i += stride2) {
-            float4 v = x4[i];
-            v.x *= c; v.y *= c; v.z *= c; v.w *= c;
-            x4[i] = v;
-        }
-        for (long i = m4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += stride2) x2[i] *= c;
-    }
+    // clip_grad_norm_ scales EVERY gradient, the buffer that is not stepped too: in this launch instead of one of its own
+    // (16-byte accesses where the buffer allows: 150 MB of decoder gradient at the Yahoo shape whenever the clip is active)
+    if (x2 && c != 1.0f) scale_range(x2, n2, c, (long)blockIdx.x, (long)gridDim.x);
     const float a = lr[0];
     const bool wb = write_back && c != 1.0f;      // g * 1 is g: the clipped-gradient write-back is skipped when the clip is inactive
-    const long stride = (long)gridDim.x * 256;
-    const bool vec = ((((uintptr_t)p) | ((uintptr_t)g)) & 15) == 0;
-    if (vec) {
-        const long n4 = n / 4;
-        float4* p4 = reinterpret_cast<float4*>(p);
-        float4* g4 = reinterpret_cast<float4*>(g);
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-            float4 gv = g4[i], pv = p4[i];
+    sgd_range(p, g, n, a, c, wb, (long)blockIdx.x, (long)gridDim.x);
+}
+
+// sgd_kernel where rows [0, V) of an embedding table (ni floats each, at element emb_off of p and g) carry a gradient on the rows of
+// the batch's tokens only and EXACT +0 everywhere else -- what lv_embed_scatter_full* leaves behind (lv_sgd_step_scale_rows_txn_f32).
+// tok[0 .. N) is that launch's sorted token list.  Workgroups [0, nb_rows): one wave per sorted position, the wave at a run's first
+// position updates the row (the others leave after two loads); the remaining workgroups run the dense code over the rest of
+// (p, g) and over x2.  An absent row would see g*c = +0 and p - a*(+0) = p: that holds bit for bit while c and a are finite and
+// not negative (a negative factor turns the product into -0, which moves a p of -0; inf or NaN make it NaN), so any other
+// (c, a) takes -- uniformly, the whole grid -- the dense walk over every row.
+__global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, float* __restrict__ g, long n,
+                                                       const float* __restrict__ lr, const float* __restrict__ coef,
+                                                       int write_back, const float* __restrict__ void_flag,
+                                                       float* __restrict__ x2, long n2, long emb_off, int V, int ni,
+                                                       const int* __restrict__ tok, int N, int nb_rows) {
+    if (void_flag && void_flag[0] != 0.f) return;
+    const float c = coef[0];
+    const float a = lr[0];
+    const bool wb = write_back && c != 1.0f;
+    const bool rows_ok = c >= 0.f && c <= 3.402823466e+38f && a >= 0.f && a <= 3.402823466e+38f;      // (false for NaN)
+    if (!rows_ok) {
+        if (x2 && c != 1.0f) scale_range(x2, n2, c, (long)blockIdx.x, (long)gridDim.x);
+        sgd_range(p, g, n, a, c, wb, (long)blockIdx.x, (long)gridDim.x);
+        return;
+    }
+    if ((int)blockIdx.x >= nb_rows) {
+        const long blk = (long)blockIdx.x - nb_rows, nblk = (long)gridDim.x - nb_rows;
+        if (x2 && c != 1.0f) scale_range(x2, n2, c, blk, nblk);
+        const long tail = emb_off + (long)V * ni;
+        if (emb_off > 0) sgd_range(p, g, emb_off, a, c, wb, blk, nblk);
+        if (tail < n) sgd_range(p + tail, g + tail, n - tail, a, c, wb, blk, nblk);
+        return;
+    }
+    const int i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    if (i >= N) return;
+    const int row = tok[i];
+    if (i > 0 && tok[i - 1] == row) return;            // not the first position of its run
+    if (row < 0 || row >= V) return;
+    float* pr = p + emb_off + (long)row * ni;
+    float* gr = g + emb_off + (long)row * ni;
+    if (ni % 4 == 0 && ((((uintptr_t)pr) | ((uintptr_t)gr)) & 15) == 0) {
+        for (int k = lane * 4; k < ni; k += 256) {
+            float4 gv = *reinterpret_cast<float4*>(gr + k), pv = *reinterpret_cast<float4*>(pr + k);
             gv.x *= c; gv.y *= c; gv.z *= c; gv.w *= c;
             pv.x -= a * gv.x; pv.y -= a * gv.y; pv.z -= a * gv.z; pv.w -= a * gv.w;
-            p4[i] = pv;
-            if (wb) g4[i] = gv;
-        }
-        for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-            const float gv = g[i] * c;
-            p[i] -= a * gv;
-            if (wb) g[i] = gv;
+            *reinterpret_cast<float4*>(pr + k) = pv;
+            if (wb) *reinterpret_cast<float4*>(gr + k) = gv;
         }
     } else {
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-            const float gv = g[i] * c;
-            p[i] -= a * gv;
-            if (wb) g[i] = gv;
+        for (int k = lane; k < ni; k += 64) {
+            const float gv = gr[k] * c;
+            pr[k] -= a * gv;
+            if (wb) gr[k] = gv;
         }
     }
 }
@@ -582,6 +644,24 @@ extern "C" int lv_sgd_step_scale_txn_f32(float* p, float* g, long n, const float
     if (n == 0 && n2 == 0) return LV_OK;
     LV_LAUNCH(sgd_kernel, dim3(lv_stream_grid(n > n2 ? n : n2)), dim3(256), 0, stream, p, g, n, lr_dev, coef_dev, write_back_clipped,
               void_flag_dev, x2, n2);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// lv_sgd_step_scale_txn_f32 where the embedding table at elements [emb_off, emb_off + V * ni) of (p, g) has a gradient on the rows
+// of the batch's tokens alone: tok[0 .. N) is the sorted token list of the lv_embed_scatter_full* launch that wrote that gradient
+// this step (every other row of it is +0, and the table is stepped with nothing added to g since).  Same results as the dense
+// entry bit for bit, same void-flag and write_back_clipped behaviour, one launch; the rows no token names are neither read nor
+// written (89 of 199 MB at the Yahoo shape) unless lr or the clip coefficient is negative or not finite (see sgd_rows_kernel).
+extern "C" int lv_sgd_step_scale_rows_txn_f32(float* p, float* g, long n, const float* lr_dev, const float* coef_dev,
+                                              int write_back_clipped, float* x2, long n2, const float* void_flag_dev, long emb_off, int V,
+                                              int ni, const int* sorted_tok, int N, void* stream) {
+    if (!p || !g || !lr_dev || !coef_dev || !void_flag_dev || !x2 || !sorted_tok || n < 0 || n2 < 0) return LV_ERR_ARG;
+    if (V <= 0 || ni <= 0 || N <= 0 || emb_off < 0 || emb_off + (long)V * ni > n) return LV_ERR_SHAPE;
+    const long rest = n - (long)V * ni;
+    const int nb_rows = (int)lv_cdiv((long)N, 4);
+    LV_LAUNCH(sgd_rows_kernel, dim3((unsigned)nb_rows + lv_stream_grid(rest > n2 ? rest : n2)), dim3(256), 0, stream, p, g, n, lr_dev, coef_dev,
+              write_back_clipped, void_flag_dev, x2, n2, emb_off, V, ni, sorted_tok, N, nb_rows);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

@@ -654,6 +654,9 @@ DUAL_WGRAD = os.environ.get("LVAE_DUAL_WGRAD", "1") != "0"
 # ... and dX with them in one grouped stream-K launch on the 256 x 256 tile where the shapes are big enough (LVAE_PAIR_WGRAD=0: the
 # separate launches, for A/B measurements)
 PAIR_WGRAD = os.environ.get("LVAE_PAIR_WGRAD", "1") != "0"
+# The decoder's three hidden-state images (O, O^T, h_prev^T) from one pass over hs (lv_cvt_bf16_hs3_f32; LVAE_HS3_CVT=0: the two
+# separate conversions, for A/B measurements)
+HS3_CVT = os.environ.get("LVAE_HS3_CVT", "1") != "0"
 
 
 class _LstmImages(object):
@@ -670,6 +673,8 @@ class _LstmImages(object):
         self.XhT = c.i16(ni + H, self.ldr)
         self.addend = None                  # unit-major copy of the Gx epilogue addend (biases / z-projection)
         self.dG = c.i16(TB, 4 * H)          # gate pre-activation grads   [T*B][4H]
+        self.hT_gen = None                  # the owner's forward generation whose h_prev image hT already holds (decoder: hs3)
+        self.hT_ld = self.ldr
 
     @property
     def XT(self):                           # layer input rows, transposed [ni][T*B]
@@ -716,11 +721,11 @@ class _LstmImages(object):
         _gemm16(lib, s, 0, TB, 4 * H, ni, P(self.X), ni, W16, ni, Gx, 4 * H,
                 add1=addend, ld1=4 * H if rows > 1 else 0, mod1=rows)
 
-    def backward(self, lib, s, dG, h_prev, WT16, dX, gW_ih, ld_gw, gW_hh, ws=None, between=None):
+    def backward(self, lib, s, dG, h_prev, WT16, dX, gW_ih, ld_gw, gW_hh, ws=None, between=None, hT_current=False):
         """dG: the f32 gate gradients, or None when the BPTT kernel already wrote their bf16 image into self.dG; WT16: the
         bf16 image of W_ih^T [ni][4H] (engine-level).  between(): called once dX is queued and before the two weight-gradient
         products (the encoder scatters its embedding gradient there, so that a data-parallel exchange of it can start under
-        the weight-gradient GEMMs)."""
+        the weight-gradient GEMMs).  hT_current: self.hT already is the image of h_prev (the decoder's forward wrote it)."""
         TB, ni, H = self.TB, self.ni, self.H
         if dG is not None:
             lib.lv_cvt_bf16_f32(dG, 4 * H, TB, 4 * H, P(self.dG), 4 * H, None, 0, s)
@@ -728,7 +733,8 @@ class _LstmImages(object):
         if PAIR_WGRAD and DUAL_WGRAD and lib.lv_gemm_b16_pair_supported(1, 4 * H, ni + H, TB, 0, TB, ni, 4 * H, wsd.numel()):
             # all three products of the layer in ONE grouped launch on the 256 x 256 tile (lv_gemm_b16_pair): [dW_ih | dW_hh] on the
             # share of the CUs its flops ask for, dX on the rest, tiles shared between workgroups summed inside the launch
-            lib.lv_cvt_bf16_f32(h_prev, H, TB, H, None, 0, P(self.hT), self.ldr, s)
+            if not hT_current:
+                lib.lv_cvt_bf16_f32(h_prev, H, TB, H, None, 0, P(self.hT), self.ldr, s)
             with _prof("gemm_bf16", 2.0 * 4 * H * (ni + H) * TB + 2.0 * TB * ni * 4 * H):
                 lib.lv_gemm_b16_pair(1, 4 * H, ni + H, TB, P(self.dG), 4 * H, P(self.XhT), self.ldr, gW_ih, ld_gw, ni, gW_hh, H,
                                      0, TB, ni, 4 * H, P(self.dG), 4 * H, WT16, 4 * H, dX, ni, P(wsd), wsd.numel(), s)
@@ -738,7 +744,8 @@ class _LstmImages(object):
         _gemm16(lib, s, 0, TB, ni, 4 * H, P(self.dG), 4 * H, WT16, 4 * H, dX, ni, ws=ws)
         if between is not None:
             between()
-        lib.lv_cvt_bf16_f32(h_prev, H, TB, H, None, 0, P(self.hT), self.ldr, s)
+        if not hT_current:
+            lib.lv_cvt_bf16_f32(h_prev, H, TB, H, None, 0, P(self.hT), self.ldr, s)
         if DUAL_WGRAD and ni % 4 == 0 and lib.lv_gemm_b16_dual_supported(4 * H, ni + H, TB, wsd.numel()):
             # both weight gradients as one product (N = ni + H columns, split between the two destinations in its reduction stage)
             with _prof("gemm_bf16", 2.0 * 4 * H * (ni + H) * TB):
@@ -767,6 +774,8 @@ class _LstmImagesMS(object):
         self.hT = c.i16(H, self.ldrd)           # h_{t-1} rows, transposed       [H][Td*B*ns]
         self.dG = c.i16(self.TBd, 4 * H)        # gate pre-activation grads      [Td*B*ns][4H]
         self.dGs = c.i16(self.TB, 4 * H)        # ... summed over the samples    [Td*B][4H]
+        self.hT_gen = None                      # as _LstmImages
+        self.hT_ld = self.ldrd
 
     def forward(self, lib, s, W16, Gxw, gather):
         """Gxw[t*B + b][4u + g] = X[t*B + b] . W_ih[g*H + u][:ni] -- the word half of the input projection, no addend (the
@@ -775,7 +784,7 @@ class _LstmImagesMS(object):
         lib.lv_embed_gather_b16(emb, ids, ids_stride, keep, kscale, T, B, self.ni, V, P(self.X), self.ni, P(self.XT), self.ldr, s)
         _gemm16(lib, s, 0, self.TB, 4 * self.H, self.ni, P(self.X), self.ni, W16, self.ni, Gxw, 4 * self.H)
 
-    def backward(self, lib, s, dG, h_prev, WT16, dX, gW_ih, ld_gw, gW_hh, ws=None):
+    def backward(self, lib, s, dG, h_prev, WT16, dX, gW_ih, ld_gw, gW_hh, ws=None, hT_current=False):
         """Arguments as _LstmImages.backward; dG must be None: self.dG holds the BPTT's bf16 gate gradients.  dGs = sum over samples (f32 sum, one rounding); dX = dGs . W_ih[:, :ni]
         and dW_ih[:, :ni] = dGs^T . X on Td * B rows; dW_hh = dG^T . h_prev on Td * B * ns rows."""
         assert dG is None
@@ -790,7 +799,8 @@ class _LstmImagesMS(object):
         else:
             _gemm16(lib, s, 0, self.TB, ni, 4 * H, P(self.dGs), 4 * H, WT16, 4 * H, dX, ni, ws=ws)
             _gemm16(lib, s, 1, 4 * H, ni, self.TB, P(self.dGs), 4 * H, P(self.XT), self.ldr, gW_ih, ld_gw, ws=ws)
-        lib.lv_cvt_bf16_f32(h_prev, H, self.TBd, H, None, 0, P(self.hT), self.ldrd, s)
+        if not hT_current:
+            lib.lv_cvt_bf16_f32(h_prev, H, self.TBd, H, None, 0, P(self.hT), self.ldrd, s)
         _gemm16(lib, s, 1, 4 * H, H, self.TBd, P(self.dG), 4 * H, P(self.hT), self.ldrd, gW_hh, H, ws=ws)
 
 
@@ -840,6 +850,9 @@ class LSTMEncoderEngine(object):
         self.persist_flags = 1                  # bit 0: hand-off granules stay in the XCD's L2 (ladder rung 0; see demote_persistent)
         self.status = None                      # device int32: a persistent launch's hand-off timeout is reported here
         self.fold = None                        # norm folding (trainer._plan_fold): {"embed": (partials tensor, norm-only flag)}
+        # (sorted token list, N) of the lv_embed_scatter_full* launch that wrote the table's gradient in the last backward(): every
+        # other row of that gradient is zero (the trainer's row-sparse SGD step); None when no such launch wrote it
+        self.embed_rows = None
         self.cache_weight_images = False        # the encoder is stepped every inner iteration: its images are rebuilt per call
         self.wgen = 0                           # bumped by the fused trainer after a raw-pointer weight update
         # bf16 configuration only: which parts of the FORWARD run f32-accurately all the same -- "gx" (the input projection
@@ -1102,6 +1115,7 @@ class LSTMEncoderEngine(object):
         if gen is not None and gen != g:
             raise _lib.LvaeError("encoder activations were overwritten by a later forward(); the HIP engine keeps "
                                  "one in-flight step per module")
+        self.embed_rows = None
         f = self.flat
         lib, s = self.lib, stream_ptr(x.device)
         V, ni, H, nz2 = self.dims()
@@ -1131,8 +1145,11 @@ class LSTMEncoderEngine(object):
             # dX -> embedding rows (the embedding table leads the flat buffer: its gradient is the first, and largest, bucket)
             self._aux.join(x.device)                   # token sort queued by forward()
             # every row of the table's gradient is written by this launch (zeros where a token does not occur): no fill in front
+            self.embed_rows = (self._sort[1], T * B)
             if self.fold and "embed" in self.fold:
                 sq, only = self.fold["embed"]         # the table gradient's squares go to the clip kernel from here (no second read)
+                if only:
+                    self.embed_rows = None
                 lib.lv_embed_scatter_full_sumsq_f32(P(w.dX), None, 1.0, P(self._sort[0]), P(self._sort[1]), T, B, P(gv["embed.weight"]), ni,
                                                     V, -1, P(sq), int(only), s)
             else:
@@ -1441,8 +1458,14 @@ class LSTMDecoderEngine(object):
                 _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, Bd, H, x.device)
             else:
                 _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device)
+        hs3 = HS3_CVT and late_mask and img is not None
+        if hs3:
+            # O, O^T (dropout_out applied) and the BPTT-side h_prev^T from ONE read of hs: backward() skips its own conversion
+            lib.lv_cvt_bf16_hs3_f32(P(w.hs), H, Td, Bd, H, P(mask_out), sc_out, P(b16.O), H, P(b16.OT), b16.ldr, P(img.hT), img.hT_ld, s)
         if b16 is not None:
-            if late_mask and mask_out is not None:
+            if hs3:
+                pass
+            elif late_mask and mask_out is not None:
                 lib.lv_cvt_bf16_keep_f32(P(w.hs, Bd * H), H, Td, Bd, H, P(mask_out), sc_out, P(b16.O), H, P(b16.OT), b16.ldr, s)
             elif late_mask:
                 lib.lv_cvt_bf16_f32(P(w.hs, Bd * H), H, Td * Bd, H, P(b16.O), H, P(b16.OT), b16.ldr, s)
@@ -1465,6 +1488,8 @@ class LSTMDecoderEngine(object):
             # rec[bd] = sum_t nll[t][bd]  (loss assembly kernel with kl weight 0); the fused driver sums nll itself
             lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
         self.gen += 1
+        if img is not None:
+            img.hT_gen = self.gen if hs3 else None
         self.last = (x, z2, mask_in, mask_out, sc_in, sc_out, B, T, self.gen)
         self.last_ns = ns
         return w.rec
@@ -1569,7 +1594,8 @@ class LSTMDecoderEngine(object):
         with ctx:
             s2 = stream_ptr(dev)
             if img is not None:                        # (_LstmImagesMS for ns > 1: sample sum, then the Td * B-row products)
-                img.backward(lib, s2, None, P(w.hs), P(self._wimg.WT), P(w.dX), P(gwih), ni + nz, P(gv["lstm.weight_hh_l0"]), ws=sws)
+                img.backward(lib, s2, None, P(w.hs), P(self._wimg.WT), P(w.dX), P(gwih), ni + nz, P(gv["lstm.weight_hh_l0"]), ws=sws,
+                             hT_current=img.hT_gen == g)
             else:
                 dG = w.dG
                 if ns > 1:

@@ -10,6 +10,7 @@ instead of one per iteration.  Data parallelism (one process per GPU) plugs in t
 """
 import collections
 import ctypes
+import os
 
 import numpy as np
 import contextlib
@@ -47,6 +48,10 @@ class _Static(object):
 # dims: 5 GB at most).  A corpus bucketed by sentence length (data/text_data.py:219-255) cycles through one shape per length plus
 # the tails: with 64 slots bench.py's 71-shape mixed pool rebuilt a slot -- one allocator request -- on every step (round 5).
 STATIC_SHAPES = 512
+
+# encoder-only SGD steps leave the embedding rows the batch does not name alone (lv_sgd_step_scale_rows_txn_f32; LVAE_ROWS_SGD=0: the
+# dense step, for A/B measurements)
+ROWS_SGD = os.environ.get("LVAE_ROWS_SGD", "1") != "0"
 
 
 def _rank_seed(seed, grad_sync):
@@ -466,7 +471,7 @@ class AggressiveTextTrainer(object):
         """True when the encoder's BPTT may be a persistent launch: a collective must then not be in flight beside it."""
         return bool(self.enc.persistent and self.enc.precision == "bf16")
 
-    def _clip_and_step(self, update, dec_ss=None):
+    def _clip_and_step(self, update, dec_ss=None, embed_rows=None):
         lib, s = self.lib, _eng.stream_ptr(self.device)
         ef, df = self.enc.flat, self.dec.flat
         # the transaction gate rides in the clip coefficient's launch: status words of both engines, data parallel also the
@@ -500,7 +505,15 @@ class AggressiveTextTrainer(object):
             b_off, b_n = 0, b.numel
             if update == "encoder" and self._fold is not None and self.decoder_grads == "norm":
                 b_off, b_n = self._fold.dec_off, self._fold.dec_end - self._fold.dec_off      # what of the decoder's gradient exists
-            lib.lv_sgd_step_scale_txn_f32(P(a.data), P(a.grad), a.numel, self._s(1), self._s(3), 1, P(b.grad, b_off), b_n, self._s(8), s)
+            emb = "embed.weight"
+            if ROWS_SGD and update == "encoder" and embed_rows is not None and ef.names[0] == emb and ef.offsets[emb] == 0:
+                # the rows of the embedding table no token of the batch names have a zero gradient (embed_rows): not touched
+                stok, n_tok = embed_rows
+                V, ni = self.enc.dims()[:2]
+                lib.lv_sgd_step_scale_rows_txn_f32(P(a.data), P(a.grad), a.numel, self._s(1), self._s(3), 1, P(b.grad, b_off), b_n,
+                                                   self._s(8), 0, V, ni, P(stok), n_tok, s)
+            else:
+                lib.lv_sgd_step_scale_txn_f32(P(a.data), P(a.grad), a.numel, self._s(1), self._s(3), 1, P(b.grad, b_off), b_n, self._s(8), s)
 
     def _sgd_momentum_step(self, update, ef, df):
         """The momentum twin of the SGD update above: lv_sgd_momentum_step_txn_f32 per stepped side (its velocity alone moves), the
@@ -589,11 +602,14 @@ class AggressiveTextTrainer(object):
         self._plan_fold(st, update)
         if self.grad_sync is not None:
             self.grad_sync.begin_step()
+        self.enc.embed_rows = None
         self._fwd_bwd(st, draw)
         dec_ss = None
         if self.grad_sync is not None:
             dec_ss = self.grad_sync.sync(self.enc.flat, self.dec.flat, update)
-        self._clip_and_step(update, dec_ss)
+        # the encoder's table gradient is this step's scatter over one sorted list, and nothing was added to it since
+        rows = self.enc.embed_rows if self.grad_sync is None and self.micro_batches == 1 else None
+        self._clip_and_step(update, dec_ss, embed_rows=rows)
 
     def step(self, x, kl_weight, noise=None, update="encoder"):
         """One body of the aggressive loop on batch x (int64 [B][T] on device).
