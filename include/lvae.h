@@ -603,6 +603,30 @@ int lv_sigmoid_bce_bwd_f32(const float* logit, const float* x, const float* drec
 /* torch.cat([img, z_transform(z).view(B, fm, 28, 28)], dim) as one NHWC tensor (dec_pixelcnn_v2.py:178-186) */
 int lv_dec_input_fwd_f32(const float* x, const float* zt, float* in5, int B, int npix, int fm, void* stream);
 int lv_dec_input_bwd_f32(const float* din5, float* dzt, int B, int npix, int fm, void* stream);
+/* Multi-sample training (image.py --nsamples; VAE.loss(x, kl_weight, nsamples = ns), dec_pixelcnn_v2.py:178-190): the decoder runs on
+ * Bd = B * ns images in row order bd = b * ns + s, and decoder row bd takes its image channel and its BCE target from image bd / ns of
+ * x [B][npix] -- no expanded copy of x.  logit [Bd * npix], rec / drec [Bd], zt [Bd][fm * npix], in5 [Bd * npix][1 + fm].  The results
+ * have the bits of the entries above run on x.repeat_interleave(ns) (ns = 1: their bits).  The input layer's backward is
+ * lv_dec_input_bwd_f32 with B := Bd. */
+int lv_sigmoid_bce_ns_fwd_f32(const float* logit, const float* x, float* rec, int B, int ns, int npix, float eps, void* stream);
+int lv_sigmoid_bce_ns_bwd_f32(const float* logit, const float* x, const float* drec, float* dlogit, int B, int ns, int npix, float eps,
+                              void* stream);
+int lv_dec_input_ns_fwd_f32(const float* x, const float* zt, float* in5, int B, int ns, int npix, int fm, void* stream);
+/* BatchNorm from the producing convolution's stage-1 partial rows at ANY row count (lv_bn_fwd_partials_f32 and
+ * lv_bn_bwd_apply_partials_f32 re-read all rows in every workgroup and stop at 1024 of them): the rows [nblk][2][C] -- a buffer of
+ * lv_bn_partial_floats(nblk, C) floats -- are reduced once, in f64 and a fixed order, by a launch of their own, and the apply pass
+ * reads the finished 2 * C floats.  Forward: lv_bn_finish_fwd_f32 (mean, invstd, running statistics with momentum and the unbiased
+ * variance; run_mean / run_var both NULL or both given), then lv_bn_fwd_stats_f32.  Backward: lv_bn_finish_bwd_f32 (sums [2][C] =
+ * this layer's (sum dv, sum dv * xhat); dbeta / dgamma = or +=), then lv_bn_bwd_stats_f32.  C: a power of two in [16, 256]. */
+long lv_bn_partial_floats(long nblk, int C);
+int lv_bn_finish_fwd_f32(const float* partial, int nblk, long P, int C, float eps, float momentum, float* mean, float* invstd,
+                         float* run_mean, float* run_var, void* stream);
+int lv_bn_fwd_stats_f32(const float* x, const float* gamma, const float* beta, const float* res, int act_elu, float* y,
+                        const float* mean, const float* invstd, long P, int C, void* stream);
+int lv_bn_finish_bwd_f32(const float* partial, int nblk, int C, float* sums, float* dgamma, float* dbeta, int accumulate_param_grads,
+                         void* stream);
+int lv_bn_bwd_stats_f32(const float* x, const float* dv, const float* sums, const float* mean, const float* invstd, const float* gamma,
+                        float* dx, long P, int C, void* stream);
 
 /* Batched, device-resident beam search for the LSTM decoder (lv_beam.hip; dec_lstm.py:163-268 for B sentences at once).  State
  * lives in caller-owned buffers laid out [B][K] (K slots per sentence): tok int64, score f32 (-inf = dead slot), h / c as two

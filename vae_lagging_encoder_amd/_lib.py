@@ -176,6 +176,14 @@ SIGNATURES = {
     "lv_sigmoid_bce_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "lv_dec_input_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_dec_input_bwd_f32": [_vp, _vp, _i, _i, _i, _vp],
+    "lv_sigmoid_bce_ns_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "lv_sigmoid_bce_ns_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "lv_dec_input_ns_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lv_bn_partial_floats": [_l, _i],
+    "lv_bn_finish_fwd_f32": [_vp, _i, _l, _i, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    "lv_bn_fwd_stats_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _l, _i, _vp],
+    "lv_bn_finish_bwd_f32": [_vp, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "lv_bn_bwd_stats_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp],
     "lv_dec_cond_ll_f32_supported": [_i, _i, _i, _i, _i],
     "lv_dec_cond_ll_f32_ws_floats": [_i, _i, _i, _i, _i],
     "lv_dec_cond_ll_f32": [_vp, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
@@ -190,7 +198,7 @@ SIGNATURES = {
 
 
 _LONG_FNS = ("lv_lstm_ws_floats", "lv_conv1x1_wgrad_ws_floats", "lv_conv1x1_blocks", "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats", "lv_conv32_wpack_floats",
-             "lv_conv32_wgrad_ws_floats", "lv_dec_cond_ll_f32_ws_floats", "lv_beam_ws_floats")
+             "lv_conv32_wgrad_ws_floats", "lv_dec_cond_ll_f32_ws_floats", "lv_beam_ws_floats", "lv_bn_partial_floats")
 
 
 class LvaeError(RuntimeError):
@@ -220,7 +228,7 @@ class Lib(object):
                            "lv_conv32_wgrad_slabs", "lv_conv32_wgrad_ws_floats", "lv_conv32_wgrad_parts", "lv_conv1x1_wgrad_parts", "lv_conv32_blocks", "lv_conv1x1_blocks", "lv_conv1x1_wgrad_ws_floats", "lv_sumsq_workspace_floats", "lv_lstm_ws_floats", "lv_bn_workspace_floats",
                            "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats",
                            "lv_pixelcnn_net_words", "lv_pixelcnn_block_words", "lv_conv32_tap_split", "lv_dec_cond_ll_f32_supported",
-                           "lv_dec_cond_ll_f32_ws_floats", "lv_beam_supported", "lv_beam_ws_floats"}
+                           "lv_dec_cond_ll_f32_ws_floats", "lv_beam_supported", "lv_beam_ws_floats", "lv_bn_partial_floats"}
 
     def __getattr__(self, name):
         if name.startswith("lv_"):

@@ -420,6 +420,55 @@ __device__ __forceinline__ void bn_block_totals(const float* __restrict__ partia
     __syncthreads();
 }
 
+// The apply loops of the BatchNorm forward and backward on statistics staged in LDS, shared by the kernels that total the partial
+// rows themselves (bn_apply_*_v4_kernel) and the ones that read finished statistics (bn_apply_*_stats_v4_kernel): one body, so the two
+// routes cannot drift apart.  xs / rs / ds: this thread's float4 items i0, i0 + 256, ..., loaded by the caller ahead of the statistics.
+template <int BN_V4_ITEMS>
+__device__ __forceinline__ void bn_v4_apply_fwd(const float4 (&xs)[BN_V4_ITEMS], const float4 (&rs)[BN_V4_ITEMS], bool res, int act,
+                                                const float* smu, const float* sis, const float* sga, const float* sbe,
+                                                float* __restrict__ y, long i0, long n4, int CT4) {
+#pragma unroll
+    for (int u = 0; u < BN_V4_ITEMS; ++u) {
+        const long i = i0 + 256 * u;
+        if (i >= n4) break;
+        const int c = 4 * (int)(i & (CT4 - 1));
+        const float4 xv = xs[u];
+        const float4 m4 = *reinterpret_cast<const float4*>(&smu[c]), i4 = *reinterpret_cast<const float4*>(&sis[c]);
+        const float4 g4 = *reinterpret_cast<const float4*>(&sga[c]), b4 = *reinterpret_cast<const float4*>(&sbe[c]);
+        float4 v;
+        v.x = (xv.x - m4.x) * i4.x * g4.x + b4.x; v.y = (xv.y - m4.y) * i4.y * g4.y + b4.y;
+        v.z = (xv.z - m4.z) * i4.z * g4.z + b4.z; v.w = (xv.w - m4.w) * i4.w * g4.w + b4.w;
+        if (res) { v.x += rs[u].x; v.y += rs[u].y; v.z += rs[u].z; v.w += rs[u].w; }
+        if (act) {
+            v.x = v.x > 0.f ? v.x : expm1f(v.x); v.y = v.y > 0.f ? v.y : expm1f(v.y);
+            v.z = v.z > 0.f ? v.z : expm1f(v.z); v.w = v.w > 0.f ? v.w : expm1f(v.w);
+        }
+        *reinterpret_cast<float4*>(y + 4 * i) = v;
+    }
+}
+
+template <int BN_V4_ITEMS>
+__device__ __forceinline__ void bn_v4_apply_bwd(const float4 (&xs)[BN_V4_ITEMS], const float4 (&ds)[BN_V4_ITEMS], const float* smu,
+                                                const float* sis, const float* sga, const float* sdg, const float* sdb, float invP,
+                                                float* __restrict__ dx, long i0, long n4, int CT4) {
+#pragma unroll
+    for (int u = 0; u < BN_V4_ITEMS; ++u) {
+        const long i = i0 + 256 * u;
+        if (i >= n4) break;
+        const int c = 4 * (int)(i & (CT4 - 1));
+        const float4 xv = xs[u], d4 = ds[u];
+        const float4 m4 = *reinterpret_cast<const float4*>(&smu[c]), i4 = *reinterpret_cast<const float4*>(&sis[c]);
+        const float4 g4 = *reinterpret_cast<const float4*>(&sga[c]);
+        const float4 dg = *reinterpret_cast<const float4*>(&sdg[c]), db = *reinterpret_cast<const float4*>(&sdb[c]);
+        float4 o;
+        o.x = g4.x * i4.x * (d4.x - db.x * invP - ((xv.x - m4.x) * i4.x) * dg.x * invP);
+        o.y = g4.y * i4.y * (d4.y - db.y * invP - ((xv.y - m4.y) * i4.y) * dg.y * invP);
+        o.z = g4.z * i4.z * (d4.z - db.z * invP - ((xv.z - m4.z) * i4.z) * dg.z * invP);
+        o.w = g4.w * i4.w * (d4.w - db.w * invP - ((xv.w - m4.w) * i4.w) * dg.w * invP);
+        *reinterpret_cast<float4*>(dx + 4 * i) = o;
+    }
+}
+
 template <int BN_V4_ITEMS>
 __global__ __launch_bounds__(256) void bn_apply_fwd_v4_kernel(const float* __restrict__ x, const float* __restrict__ partial, int nblk,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -460,24 +509,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_v4_kernel(const float* __res
         }
     }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < BN_V4_ITEMS; ++u) {
-        const long i = i0 + 256 * u;
-        if (i >= n4) break;
-        const int c = 4 * (int)(i & (CT4 - 1));
-        const float4 xv = xs[u];
-        const float4 m4 = *reinterpret_cast<const float4*>(&smu[c]), i4 = *reinterpret_cast<const float4*>(&sis[c]);
-        const float4 g4 = *reinterpret_cast<const float4*>(&sga[c]), b4 = *reinterpret_cast<const float4*>(&sbe[c]);
-        float4 v;
-        v.x = (xv.x - m4.x) * i4.x * g4.x + b4.x; v.y = (xv.y - m4.y) * i4.y * g4.y + b4.y;
-        v.z = (xv.z - m4.z) * i4.z * g4.z + b4.z; v.w = (xv.w - m4.w) * i4.w * g4.w + b4.w;
-        if (res) { v.x += rs[u].x; v.y += rs[u].y; v.z += rs[u].z; v.w += rs[u].w; }
-        if (act) {
-            v.x = v.x > 0.f ? v.x : expm1f(v.x); v.y = v.y > 0.f ? v.y : expm1f(v.y);
-            v.z = v.z > 0.f ? v.z : expm1f(v.z); v.w = v.w > 0.f ? v.w : expm1f(v.w);
-        }
-        *reinterpret_cast<float4*>(y + 4 * i) = v;
-    }
+    bn_v4_apply_fwd<BN_V4_ITEMS>(xs, rs, res != nullptr, act, smu, sis, sga, sbe, y, i0, n4, CT4);
 }
 
 template <int BN_V4_ITEMS>
@@ -512,22 +544,7 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_v4_kernel(const float* __res
         }
     }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < BN_V4_ITEMS; ++u) {
-        const long i = i0 + 256 * u;
-        if (i >= n4) break;
-        const int c = 4 * (int)(i & (CT4 - 1));
-        const float4 xv = xs[u], d4 = ds[u];
-        const float4 m4 = *reinterpret_cast<const float4*>(&smu[c]), i4 = *reinterpret_cast<const float4*>(&sis[c]);
-        const float4 g4 = *reinterpret_cast<const float4*>(&sga[c]);
-        const float4 dg = *reinterpret_cast<const float4*>(&sdg[c]), db = *reinterpret_cast<const float4*>(&sdb[c]);
-        float4 o;
-        o.x = g4.x * i4.x * (d4.x - db.x * invP - ((xv.x - m4.x) * i4.x) * dg.x * invP);
-        o.y = g4.y * i4.y * (d4.y - db.y * invP - ((xv.y - m4.y) * i4.y) * dg.y * invP);
-        o.z = g4.z * i4.z * (d4.z - db.z * invP - ((xv.z - m4.z) * i4.z) * dg.z * invP);
-        o.w = g4.w * i4.w * (d4.w - db.w * invP - ((xv.w - m4.w) * i4.w) * dg.w * invP);
-        *reinterpret_cast<float4*>(dx + 4 * i) = o;
-    }
+    bn_v4_apply_bwd<BN_V4_ITEMS>(xs, ds, smu, sis, sga, sdg, sdb, invP, dx, i0, n4, CT4);
 }
 
 static inline bool bn_v4_ok(int C) { return C >= 16 && C <= 256 && (C & (C - 1)) == 0; }
@@ -606,6 +623,165 @@ __global__ __launch_bounds__(256) void dec_input_bwd_kernel(const float* __restr
     const int c = (int)((i / npix) % fm);
     const long b = i / ((long)npix * fm);
     dzt[i] = din5[(b * npix + pix) * (1 + fm) + 1 + c];
+}
+
+// ---- multi-sample training (image.py --nsamples: VAE.loss(x, kl_weight, nsamples = ns)) -----------------------------------------
+// The decoder runs on Bd = B * ns images in the reference's row order bd = b * ns + s (dec_pixelcnn_v2.py:178-190); its image
+// channel and its BCE target are image bd / ns of x [B][npix]: no expanded copy of x exists.  Same work split, same summation
+// order as the ns = 1 twins above, so that they give the twins' bits on an explicitly repeated x (and at ns = 1).
+__global__ __launch_bounds__(256) void sigmoid_bce_ns_fwd_kernel(const float* __restrict__ logit, const float* __restrict__ x,
+                                                                 float* __restrict__ rec, int ns, int npix, float eps) {
+    __shared__ float red[4];
+    const int bd = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const float* xb = x + (long)(bd / ns) * npix;
+    float s = 0.f;
+    for (int i = tid; i < npix; i += 256) {
+        const float p = 1.f / (1.f + expf(-logit[(long)bd * npix + i]));
+        const float xv = xb[i];
+        s += logf(p + eps) * xv + logf(1.f - p + eps) * (1.f - xv);
+    }
+    s = lv_wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) rec[bd] = -((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+__global__ __launch_bounds__(256) void sigmoid_bce_ns_bwd_kernel(const float* __restrict__ logit, const float* __restrict__ x,
+                                                                 const float* __restrict__ drec, float* __restrict__ dlogit,
+                                                                 int ns, int npix, long n, float eps) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // over Bd*npix
+    if (i >= n) return;
+    const long bd = i / npix;
+    const int pix = (int)(i - bd * npix);
+    const float p = 1.f / (1.f + expf(-logit[i]));
+    const float xv = x[(bd / ns) * npix + pix];
+    const float dp = -(xv / (p + eps) - (1.f - xv) / (1.f - p + eps));
+    dlogit[i] = drec[bd] * dp * p * (1.f - p);
+}
+
+// in5[bd][pix][0] = x[bd / ns][pix]; in5[bd][pix][1+c] = zt[bd][c*npix + pix]
+__global__ __launch_bounds__(256) void dec_input_ns_fwd_kernel(const float* __restrict__ x, const float* __restrict__ zt,
+                                                               float* __restrict__ in5, int ns, int npix, int fm, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;     // over Bd*npix*(1+fm)
+    if (i >= n) return;
+    const int C = 1 + fm;
+    const int c = (int)(i % C);
+    const long p = i / C;
+    const int pix = (int)(p % npix);
+    const long bd = p / npix;
+    in5[i] = c == 0 ? x[(bd / ns) * npix + pix] : zt[(bd * fm + (c - 1)) * npix + pix];
+}
+
+// ---- BatchNorm from the producers' partial sums at ANY number of partial rows: finish once, then apply -----------------------------
+// The apply kernels above re-derive the per-channel totals from all partial rows in every workgroup, which is why their row count is
+// capped (BN_BLOCKS): past the cap that prologue would outgrow the pass itself.  Here the rows are reduced ONCE by a launch of their
+// own -- workgroup g owns channels 4g .. 4g+3, thread t adds rows t, t + 256, ... in f64, then lanes, then the four waves, a fixed
+// order -- and the apply kernels read the finished 2*C floats.  Two ordinary launches, no hand-off between workgroups.
+// MODE 0: (sum x, sum x^2) -> mean, invstd, running statistics.  MODE 1: (sum dv, sum dv*xhat) -> sums [2][C] = (dbeta, dgamma) of this
+// layer and (=|+=) the parameter gradients.
+constexpr int BNF_BATCH = 4;             // partial rows a thread has in flight per round trip
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_finish_rows_kernel(const float* __restrict__ partial, int nblk, long P, int C, float eps,
+                                                             float momentum, float* __restrict__ out0, float* __restrict__ out1,
+                                                             float* __restrict__ p0, float* __restrict__ p1, int accumulate) {
+    __shared__ double red[4][8];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c0 = 4 * (int)blockIdx.x;
+    const float* base = partial + c0;
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < nblk; b += 256 * BNF_BATCH) {
+        float4 v0[BNF_BATCH], v1[BNF_BATCH];
+#pragma unroll
+        for (int u = 0; u < BNF_BATCH; ++u) {                 // unconditional loads from clamped rows, masked when added
+            const int bb = b + 256 * u;
+            const long r = bb < nblk ? bb : b;
+            v0[u] = *reinterpret_cast<const float4*>(base + (r * 2 + 0) * C);
+            v1[u] = *reinterpret_cast<const float4*>(base + (r * 2 + 1) * C);
+        }
+#pragma unroll
+        for (int u = 0; u < BNF_BATCH; ++u) {
+            if (b + 256 * u < nblk) {
+                a[0] += (double)v0[u].x; a[1] += (double)v0[u].y; a[2] += (double)v0[u].z; a[3] += (double)v0[u].w;
+                a[4] += (double)v1[u].x; a[5] += (double)v1[u].y; a[6] += (double)v1[u].z; a[7] += (double)v1[u].w;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = lv_wave_sum(a[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) red[wv][k] = a[k];
+    }
+    __syncthreads();
+    if (tid >= 4) return;
+    const int c = c0 + tid;
+    const double s = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    const double q = (red[0][4 + tid] + red[1][4 + tid]) + (red[2][4 + tid] + red[3][4 + tid]);
+    if (MODE == 0) {
+        const double m = s / (double)P;
+        double var = q / (double)P - m * m;
+        if (var < 0.0) var = 0.0;
+        out0[c] = (float)m;
+        out1[c] = (float)(1.0 / sqrt(var + (double)eps));
+        if (p0) {
+            const double unb = P > 1 ? var * (double)P / (double)(P - 1) : var;
+            p0[c] = (float)((1.0 - momentum) * (double)p0[c] + momentum * m);
+            p1[c] = (float)((1.0 - momentum) * (double)p1[c] + momentum * unb);
+        }
+    } else {
+        out0[c] = (float)s;                                   // sums[0][c]: this layer's dbeta
+        out0[C + c] = (float)q;                               // sums[1][c]: this layer's dgamma
+        p1[c] = (float)(s + (accumulate ? (double)p1[c] : 0.0));
+        p0[c] = (float)(q + (accumulate ? (double)p0[c] : 0.0));
+    }
+}
+
+// bn_apply_fwd_v4_kernel on finished statistics: 2*C floats per workgroup instead of all partial rows
+template <int BN_V4_ITEMS>
+__global__ __launch_bounds__(256) void bn_apply_fwd_stats_v4_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                                    const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, const float* __restrict__ res, int act,
+                                                                    float* __restrict__ y, long P, int C) {
+    __shared__ __attribute__((aligned(16))) float smu[256], sis[256], sga[256], sbe[256];
+    const int tid = (int)threadIdx.x;
+    const long n4 = P * (C >> 2);
+    const int CT4 = C >> 2;
+    const long i0 = (long)blockIdx.x * (256 * BN_V4_ITEMS) + tid;
+    float4 xs[BN_V4_ITEMS], rs[BN_V4_ITEMS];
+#pragma unroll
+    for (int u = 0; u < BN_V4_ITEMS; ++u) {
+        const long i = i0 + 256 * u;
+        const long ii = i < n4 ? i : 0;
+        xs[u] = *reinterpret_cast<const float4*>(x + 4 * ii);
+        if (res) rs[u] = *reinterpret_cast<const float4*>(res + 4 * ii);
+    }
+    if (tid < C) { smu[tid] = mean[tid]; sis[tid] = invstd[tid]; sga[tid] = gamma[tid]; sbe[tid] = beta[tid]; }
+    __syncthreads();
+    bn_v4_apply_fwd<BN_V4_ITEMS>(xs, rs, res != nullptr, act, smu, sis, sga, sbe, y, i0, n4, CT4);
+}
+
+// bn_apply_bwd_v4_kernel on finished sums [2][C] = (sum dv, sum dv * xhat)
+template <int BN_V4_ITEMS>
+__global__ __launch_bounds__(256) void bn_apply_bwd_stats_v4_kernel(const float* __restrict__ x, const float* __restrict__ dv,
+                                                                    const float* __restrict__ sums, const float* __restrict__ mean,
+                                                                    const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                    float* __restrict__ dx, long P, int C, float invP) {
+    __shared__ __attribute__((aligned(16))) float smu[256], sis[256], sga[256], sdg[256], sdb[256];
+    const int tid = (int)threadIdx.x;
+    const long n4 = P * (C >> 2);
+    const int CT4 = C >> 2;
+    const long i0 = (long)blockIdx.x * (256 * BN_V4_ITEMS) + tid;
+    float4 xs[BN_V4_ITEMS], ds[BN_V4_ITEMS];
+#pragma unroll
+    for (int u = 0; u < BN_V4_ITEMS; ++u) {
+        const long i = i0 + 256 * u;
+        const long ii = i < n4 ? i : 0;
+        xs[u] = *reinterpret_cast<const float4*>(x + 4 * ii);
+        ds[u] = *reinterpret_cast<const float4*>(dv + 4 * ii);
+    }
+    if (tid < C) { smu[tid] = mean[tid]; sis[tid] = invstd[tid]; sga[tid] = gamma[tid]; sdb[tid] = sums[tid]; sdg[tid] = sums[C + tid]; }
+    __syncthreads();
+    bn_v4_apply_bwd<BN_V4_ITEMS>(xs, ds, smu, sis, sga, sdg, sdb, invP, dx, i0, n4, CT4);
 }
 
 static inline unsigned conv_grid(long n) {
@@ -856,6 +1032,86 @@ extern "C" int lv_dec_input_bwd_f32(const float* din5, float* dzt, int B, int np
     if (!din5 || !dzt || B <= 0 || npix <= 0 || fm <= 0) return LV_ERR_ARG;
     const long n = (long)B * npix * fm;
     LV_LAUNCH(dec_input_bwd_kernel, dim3((unsigned)lv_cdiv(n, 256)), dim3(256), 0, stream, din5, dzt, npix, fm, n);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// ---- multi-sample twins of the three entries above: x [B][npix] serves the ns decoder rows bd = b*ns + s of image b -------------
+extern "C" int lv_sigmoid_bce_ns_fwd_f32(const float* logit, const float* x, float* rec, int B, int ns, int npix, float eps,
+                                         void* stream) {
+    if (!logit || !x || !rec || B <= 0 || ns <= 0 || npix <= 0) return LV_ERR_ARG;
+    if ((long)B * ns > 0x7fffffffL) return LV_ERR_SHAPE;
+    LV_LAUNCH(sigmoid_bce_ns_fwd_kernel, dim3((unsigned)(B * ns)), dim3(256), 0, stream, logit, x, rec, ns, npix, eps);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+extern "C" int lv_sigmoid_bce_ns_bwd_f32(const float* logit, const float* x, const float* drec, float* dlogit, int B, int ns, int npix,
+                                         float eps, void* stream) {
+    if (!logit || !x || !drec || !dlogit || B <= 0 || ns <= 0 || npix <= 0) return LV_ERR_ARG;
+    const long n = (long)B * ns * npix;
+    LV_LAUNCH(sigmoid_bce_ns_bwd_kernel, dim3((unsigned)lv_cdiv(n, 256)), dim3(256), 0, stream, logit, x, drec, dlogit, ns, npix, n, eps);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+extern "C" int lv_dec_input_ns_fwd_f32(const float* x, const float* zt, float* in5, int B, int ns, int npix, int fm, void* stream) {
+    if (!x || !zt || !in5 || B <= 0 || ns <= 0 || npix <= 0 || fm < 0) return LV_ERR_ARG;
+    const long n = (long)B * ns * npix * (1 + fm);
+    LV_LAUNCH(dec_input_ns_fwd_kernel, dim3((unsigned)lv_cdiv(n, 256)), dim3(256), 0, stream, x, zt, in5, ns, npix, fm, n);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// ---- finish-then-apply BatchNorm: the producers' partial rows [nblk][2][C] at any nblk ---------------------------------------------
+extern "C" long lv_bn_partial_floats(long nblk, int C) { return (nblk > 0 ? nblk : 1) * 2 * (long)(C > 0 ? C : 1); }
+
+// rows -> mean, invstd (saved) and the running statistics (momentum, unbiased variance; run_mean / run_var may both be NULL)
+extern "C" int lv_bn_finish_fwd_f32(const float* partial, int nblk, long P, int C, float eps, float momentum, float* mean, float* invstd,
+                                    float* run_mean, float* run_var, void* stream) {
+    if (!partial || !mean || !invstd || (!run_mean) != (!run_var)) return LV_ERR_ARG;
+    if (P <= 0 || C <= 0 || nblk <= 0) return LV_ERR_SHAPE;
+    if (!bn_v4_ok(C)) return LV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)partial) & 15) != 0) return LV_ERR_ALIGN;
+    LV_LAUNCH((bn_finish_rows_kernel<0>), dim3((unsigned)(C >> 2)), dim3(256), 0, stream, partial, nblk, P, C, eps, momentum, mean, invstd,
+              run_mean, run_var, 0);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// y = act((x - mean) * invstd * gamma + beta (+ res)) on finished statistics
+extern "C" int lv_bn_fwd_stats_f32(const float* x, const float* gamma, const float* beta, const float* res, int act_elu, float* y,
+                                   const float* mean, const float* invstd, long P, int C, void* stream) {
+    if (!x || !gamma || !beta || !y || !mean || !invstd) return LV_ERR_ARG;
+    if (P <= 0 || C <= 0) return LV_ERR_SHAPE;
+    if (!bn_v4_ok(C)) return LV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) != 0) return LV_ERR_ALIGN;
+    BN_APPLY_LAUNCH(bn_apply_fwd_stats_v4_kernel, P * (C >> 2), C, stream, x, mean, invstd, gamma, beta, res, act_elu, y, P, C);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// rows of (sum dv, sum dv * xhat) -> sums [2][C] (this layer's dbeta, dgamma) and dgamma / dbeta (=|+=)
+extern "C" int lv_bn_finish_bwd_f32(const float* partial, int nblk, int C, float* sums, float* dgamma, float* dbeta,
+                                    int accumulate_param_grads, void* stream) {
+    if (!partial || !sums || !dgamma || !dbeta) return LV_ERR_ARG;
+    if (C <= 0 || nblk <= 0) return LV_ERR_SHAPE;
+    if (!bn_v4_ok(C)) return LV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)partial) & 15) != 0) return LV_ERR_ALIGN;
+    LV_LAUNCH((bn_finish_rows_kernel<1>), dim3((unsigned)(C >> 2)), dim3(256), 0, stream, partial, nblk, 1L, C, 0.f, 0.f, sums,
+              (float*)nullptr, dgamma, dbeta, accumulate_param_grads);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// dx = gamma * invstd * (dv - sums[0]/P - xhat * sums[1]/P)
+extern "C" int lv_bn_bwd_stats_f32(const float* x, const float* dv, const float* sums, const float* mean, const float* invstd,
+                                   const float* gamma, float* dx, long P, int C, void* stream) {
+    if (!x || !dv || !sums || !mean || !invstd || !gamma || !dx) return LV_ERR_ARG;
+    if (P <= 0 || C <= 0) return LV_ERR_SHAPE;
+    if (!bn_v4_ok(C)) return LV_ERR_UNSUPPORTED;
+    if ((((uintptr_t)x | (uintptr_t)dv | (uintptr_t)dx) & 15) != 0) return LV_ERR_ALIGN;
+    BN_APPLY_LAUNCH(bn_apply_bwd_stats_v4_kernel, P * (C >> 2), C, stream, x, dv, sums, mean, invstd, gamma, dx, P, C, 1.0f / (float)P);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

@@ -29,7 +29,7 @@ class Act(object):
         return self.N * self.H * self.W
 
 
-_BN_MAX_BLOCKS = 1024         # partial blocks a BN workspace holds (lv_bn_workspace_floats)
+_BN_MAX_BLOCKS = 1024         # partial rows the apply kernels that total the rows themselves accept (lv_bn_workspace_floats)
 CONV_TERMS = {"f32": 0, "bf16x3": 3, "bf16": 1}      # precision -> terms of lv_conv32_b16 / lv_conv32_wgrad_b16 (0: the exact-f32 entries)
 
 
@@ -44,7 +44,8 @@ def pack_conv32(lib, s, ent):
 
 
 class Tape(object):
-    def __init__(self, device, precision="f32", train=True, wcache=None, wver=None, fuse_bn_bwd=True):
+    def __init__(self, device, precision="f32", train=True, wcache=None, wver=None, fuse_bn_bwd=True, bn_partial_cap=_BN_MAX_BLOCKS,
+                 counters=None):
         self.device = torch.device(device)
         self.lib = _eng.backend_for(self.device)
         # "f32": exact-f32 matrix pipe everywhere.  "bf16x3": the direct 32 -> 32 convolutions with every operand split into two
@@ -57,6 +58,11 @@ class Tape(object):
         # stage 1 of a BatchNorm's backward in the epilogue of the data-gradient convolution in front of it (_fused_bn_bwd_ok);
         # an engine attribute (fuse_bn_bwd), off = the two-launch BatchNorm backward everywhere
         self.fuse_bn_bwd = bool(fuse_bn_bwd)
+        # a producing convolution that leaves more partial rows than this has them reduced once by a launch of its own and the
+        # BatchNorm applied from the finished statistics (_bn_route); an engine attribute (bn_partial_cap), float("inf") = the
+        # fusions are dropped past 1024 rows instead.  counters: the owning engine's launch counts of that route
+        self.bn_partial_cap = bn_partial_cap
+        self.counters = counters if counters is not None else {"bn_finish_fwd": 0, "bn_finish_bwd": 0}
         self.train = train
         self.back = []
         self.grads = {}
@@ -75,12 +81,25 @@ class Tape(object):
     def f32(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
 
-    def bn_ws(self, C):
+    def bn_ws(self, C, nblk=0):
+        """The BatchNorm workspace of width C; nblk > 1024: with room for that many partial rows of a producing convolution."""
+        n = self.lib.lv_bn_workspace_floats(C) + 2 * C
+        if nblk > _BN_MAX_BLOCKS:
+            n = max(n, int(self.lib.lv_bn_partial_floats(nblk, C)) + 2 * C)
         w = self._bn_ws.get(C)
-        if w is None:
-            w = self.f32(self.lib.lv_bn_workspace_floats(C) + 2 * C)
+        if w is None or w.numel() < n:
+            w = self.f32(n)
             self._bn_ws[C] = w
         return w
+
+    def _bn_route(self, nblk):
+        """What a BatchNorm does with nblk partial rows of its producer: "finish" (reduce them once, then apply), "totals" (the apply
+        kernel totals them itself: at most 1024 rows), or None (no fusion: the BatchNorm makes its own statistics pass)."""
+        if nblk <= 0:
+            return None
+        if nblk > self.bn_partial_cap:
+            return "finish"
+        return "totals" if nblk <= _BN_MAX_BLOCKS else None
 
     def bump_bn_counters(self):
         """BatchNorm2d.num_batches_tracked += 1 for every layer this forward ran in train mode: one fused launch."""
@@ -209,7 +228,7 @@ class Tape(object):
         """The data gradient wrt x may leave its kernel as the dv of the BatchNorm that produced x: x is a BatchNorm output read by
         this convolution alone, nothing has been added to its gradient, and the partial blocks fit."""
         return (self.fuse_bn_bwd and self.train and x.bn_src is not None and x.uses == 1 and self.grads.get(id(x)) is None
-                and 0 < nblk <= _BN_MAX_BLOCKS)
+                and self._bn_route(nblk) is not None)
 
     def _conv32(self, x, weight, gview, k, nt, mask, bn_stats=False):
         """32 -> 32 channel k x k convolution on a 28 x 28 map without an im2col buffer (lv_conv_direct.hip): forward and data
@@ -230,15 +249,16 @@ class Tape(object):
         y = self.f32(x.P, 32)
         out = Act(y, x.N, 28, 28, 32)
         with _eng._prof("conv_direct", 2.0 * x.P * 1024 * nt):            # flops over the taps the mask keeps
-            stats = bn_stats and lib.lv_conv32_blocks(x.N) <= _BN_MAX_BLOCKS
+            nblk_f = lib.lv_conv32_blocks(x.N)
+            stats = bn_stats and self._bn_route(nblk_f) is not None
             if terms:
-                lib.lv_conv32_b16(P(x.t), P(wp), P(y), P(self.bn_ws(32)) if stats else None, x.N, k, nt, 0, 0, terms, s)
+                lib.lv_conv32_b16(P(x.t), P(wp), P(y), P(self.bn_ws(32, nblk_f)) if stats else None, x.N, k, nt, 0, 0, terms, s)
             elif stats:
-                lib.lv_conv32_bnstat_f32(P(x.t), P(wp), P(y), P(self.bn_ws(32)), x.N, k, nt, s)
+                lib.lv_conv32_bnstat_f32(P(x.t), P(wp), P(y), P(self.bn_ws(32, nblk_f)), x.N, k, nt, s)
             else:
                 lib.lv_conv32_f32(P(x.t), P(wp), P(y), x.N, k, nt, 0, 0, s)
             if stats:
-                out.bn_nblk = lib.lv_conv32_blocks(x.N)
+                out.bn_nblk = nblk_f
 
         def bwd():
             dy = self.grad_of(out)
@@ -279,9 +299,10 @@ class Tape(object):
         y = self.f32(x.P, Cout)
         out = Act(y, x.N, x.H, x.W, Cout)
         with _eng._prof("conv_pointwise", 4.0 * x.P * (Cin + Cout)):       # HBM-bound: bytes of the activation in and out
-            if bn_stats and lib.lv_conv1x1_blocks(x.P) <= _BN_MAX_BLOCKS:
-                lib.lv_conv1x1_bnstat_f32(P(x.t), P(weight), P(y), P(self.bn_ws(Cout)), x.P, Cin, Cout, s)
-                out.bn_nblk = int(lib.lv_conv1x1_blocks(x.P))
+            nblk_f = int(lib.lv_conv1x1_blocks(x.P))
+            if bn_stats and self._bn_route(nblk_f) is not None:
+                lib.lv_conv1x1_bnstat_f32(P(x.t), P(weight), P(y), P(self.bn_ws(Cout, nblk_f)), x.P, Cin, Cout, s)
+                out.bn_nblk = nblk_f
             else:
                 lib.lv_conv1x1_f32(P(x.t), P(weight), P(y), x.P, Cin, Cout, 0, 0, s)
 
@@ -324,7 +345,15 @@ class Tape(object):
         nres = 1 if res is not None else 0
         self._bn_prof = _eng._prof("batchnorm", 4.0 * Pn * C * (2 + nres + (0 if (self.train and x.bn_nblk) else 1 if self.train else 0)))
         self._bn_prof.__enter__()
-        if self.train and x.bn_nblk:
+        if self.train and x.bn_nblk and self._bn_route(x.bn_nblk) == "finish":
+            # ... in more rows than an apply workgroup should total by itself: one launch finishes the statistics, the apply reads them
+            lib.lv_bn_finish_fwd_f32(P(self.bn_ws(C, x.bn_nblk)), x.bn_nblk, Pn, C, bn.eps, bn.momentum, P(mean), P(invstd),
+                                     P(bn.running_mean), P(bn.running_var), s)
+            lib.lv_bn_fwd_stats_f32(P(x.t), P(bn.weight), P(bn.bias), P(res.t) if res is not None else None, int(act), P(y), P(mean),
+                                    P(invstd), Pn, C, s)
+            self.counters["bn_finish_fwd"] += 1
+            self.bn_seen.append(bn.num_batches_tracked)
+        elif self.train and x.bn_nblk:
             # the producing convolution left the per-channel partial sums in the workspace
             lib.lv_bn_fwd_partials_f32(P(x.t), P(bn.weight), P(bn.bias), P(res.t) if res is not None else None, int(act), P(y),
                                        P(mean), P(invstd), P(bn.running_mean), P(bn.running_var), bn.eps, bn.momentum,
@@ -353,8 +382,14 @@ class Tape(object):
                 # stage 1 (dv and the partial sums) came out of the reading convolution's data-gradient kernel: the apply pass alone
                 dv, part, nblk = out.fused
                 with _eng._prof("batchnorm", 4.0 * Pn * C * 3):
-                    lib.lv_bn_bwd_apply_partials_f32(P(x.t), P(dv), P(part), nblk, P(mean), P(invstd), P(bn.weight), P(dx), P(g_gamma),
-                                                     P(g_beta), 0, Pn, C, s)
+                    if self._bn_route(nblk) == "finish":
+                        sums = self.f32(2 * C)
+                        lib.lv_bn_finish_bwd_f32(P(part), nblk, C, P(sums), P(g_gamma), P(g_beta), 0, s)
+                        lib.lv_bn_bwd_stats_f32(P(x.t), P(dv), P(sums), P(mean), P(invstd), P(bn.weight), P(dx), Pn, C, s)
+                        self.counters["bn_finish_bwd"] += 1
+                    else:
+                        lib.lv_bn_bwd_apply_partials_f32(P(x.t), P(dv), P(part), nblk, P(mean), P(invstd), P(bn.weight), P(dx),
+                                                         P(g_gamma), P(g_beta), 0, Pn, C, s)
                 if res is not None and res.needs_grad:
                     self.add_grad(res, dv)
                 if x.needs_grad:
@@ -465,16 +500,20 @@ def pixelcnn_block(tp, flat, blk, x):
     return tp.bn(h, m[7], _gv(flat, m[7].weight), _gv(flat, m[7].bias), res=x, act=True)
 
 
-def decoder_forward(tp, flat, dec, x_img, z2d, zact):
-    """x_img [B,1,28,28] binarised, z2d [B,nz] -> (logit Act [B*784,1], xflat [B*784])."""
+def decoder_forward(tp, flat, dec, x_img, z2d, zact, ns=1):
+    """x_img [B,1,28,28] binarised, z2d [B*ns,nz] (row b*ns + s: sample s of image b) -> (logit Act [B*ns*784,1], xflat [B*784])."""
     lib, s = tp.lib, tp.s()
-    B = x_img.shape[0]
+    Bx = x_img.shape[0]
+    B = Bx * ns                         # decoder images
     npix, fm = 28 * 28, dec.fm_latent
-    xflat = x_img.reshape(B * npix).contiguous().float()
+    xflat = x_img.reshape(Bx * npix).contiguous().float()
     lin = dec.z_transform[0]
     zt = tp.linear(z2d, zact, lin.weight, lin.bias, _gv(flat, lin.weight), _gv(flat, lin.bias))      # [B, fm*784]
     in5_t = tp.f32(B * npix, 1 + fm)
-    lib.lv_dec_input_fwd_f32(P(xflat), P(zt.t), P(in5_t), B, npix, fm, s)
+    if ns == 1:
+        lib.lv_dec_input_fwd_f32(P(xflat), P(zt.t), P(in5_t), B, npix, fm, s)
+    else:                               # the image channel of row bd is image bd // ns: x is never expanded
+        lib.lv_dec_input_ns_fwd_f32(P(xflat), P(zt.t), P(in5_t), Bx, ns, npix, fm, s)
     tp.in5 = in5_t                      # (PixelCNNSampler reads the latent maps from here)
     in5 = Act(in5_t, B, 28, 28, 1 + fm)
 
@@ -515,6 +554,8 @@ class ImageEncoderEngine(object):
         self.flat = None
         self.precision = "f32"
         self.fuse_bn_bwd = True
+        self.bn_partial_cap = _BN_MAX_BLOCKS      # see Tape: partial rows past which a BatchNorm's statistics are finished by their own launch
+        self.launches = {"bn_finish_fwd": 0, "bn_finish_bwd": 0}
         self.gen = 0
 
     def ensure(self, device):
@@ -526,7 +567,8 @@ class ImageEncoderEngine(object):
 
     def forward(self, x_img):
         f = self.ensure(x_img.device)
-        self.tape = Tape(x_img.device, self.precision, train=self.m.training, fuse_bn_bwd=self.fuse_bn_bwd)
+        self.tape = Tape(x_img.device, self.precision, train=self.m.training, fuse_bn_bwd=self.fuse_bn_bwd,
+                         bn_partial_cap=self.bn_partial_cap, counters=self.launches)
         self.out = encoder_forward(self.tape, f, self.m, x_img)
         self.tape.bump_bn_counters()
         self.gen += 1
@@ -545,6 +587,9 @@ class ImageDecoderEngine(object):
         self.flat = None
         self.precision = "f32"
         self.fuse_bn_bwd = True
+        self.bn_partial_cap = _BN_MAX_BLOCKS      # see Tape: partial rows past which a BatchNorm's statistics are finished by their own launch
+        self.launches = {"bn_finish_fwd": 0, "bn_finish_bwd": 0}
+        self.ns = 1               # samples per image of the last forward()
         self.gen = 0
         self.wgen = 0             # bumped by the fused trainer after a raw-pointer weight update
         self._wcache = {}
@@ -571,30 +616,42 @@ class ImageDecoderEngine(object):
                 pack_conv32(lib, s, ent)
                 ent["ver"] = ver
 
-    def forward(self, x_img, z2d):
-        """-> rec [B] (BCE summed over pixels)."""
+    def forward(self, x_img, z2d, ns=1):
+        """-> rec [B*ns] (BCE summed over pixels).  ns > 1: z2d holds ns samples per image (row b*ns + s) and the decoder runs on
+        B*ns images, the ns rows of an image sharing its pixels (dec_pixelcnn_v2.py:178-190 without the expanded x)."""
         f = self.ensure(x_img.device)
         wver = self.weights_version()
-        tp = Tape(x_img.device, self.precision, train=self.m.training, wcache=self._wcache, wver=wver, fuse_bn_bwd=self.fuse_bn_bwd)
+        tp = Tape(x_img.device, self.precision, train=self.m.training, wcache=self._wcache, wver=wver, fuse_bn_bwd=self.fuse_bn_bwd,
+                  bn_partial_cap=self.bn_partial_cap, counters=self.launches)
         self.tape = tp
         B = x_img.shape[0]
-        self.zact = Act(z2d.contiguous(), B, 1, 1, z2d.shape[1])
-        self.logit, self.xflat = decoder_forward(tp, f, self.m, x_img, self.zact.t, self.zact)
+        if z2d.shape[0] != B * ns:
+            raise ValueError("z2d has %d rows for %d images x %d samples" % (z2d.shape[0], B, ns))
+        self.ns = ns
+        self.zact = Act(z2d.contiguous(), B * ns, 1, 1, z2d.shape[1])
+        self.logit, self.xflat = decoder_forward(tp, f, self.m, x_img, self.zact.t, self.zact, ns)
         tp.bump_bn_counters()
-        self.rec = tp.f32(B)
-        tp.lib.lv_sigmoid_bce_fwd_f32(P(self.logit.t), P(self.xflat), P(self.rec), B, 28 * 28, 1e-12, tp.s())
+        self.rec = tp.f32(B * ns)
+        if ns == 1:
+            tp.lib.lv_sigmoid_bce_fwd_f32(P(self.logit.t), P(self.xflat), P(self.rec), B, 28 * 28, 1e-12, tp.s())
+        else:
+            tp.lib.lv_sigmoid_bce_ns_fwd_f32(P(self.logit.t), P(self.xflat), P(self.rec), B, ns, 28 * 28, 1e-12, tp.s())
         self.gen += 1
         return self.rec
 
     def backward(self, drec, gen=None):
-        """drec [B] -> parameter grads in self.flat.grad; returns dz [B, nz]."""
+        """drec [B*ns] -> parameter grads in self.flat.grad; returns dz [B*ns, nz]."""
         if gen is not None and gen != self.gen:
             raise _lib.LvaeError("decoder activations were overwritten by a later forward()")
         tp = self.tape
         B = self.rec.shape[0]
         dlogit = tp.f32(B * 28 * 28, 1)
         drec_c = drec.contiguous()
-        tp.lib.lv_sigmoid_bce_bwd_f32(P(self.logit.t), P(self.xflat), P(drec_c), P(dlogit), B, 28 * 28, 1e-12, tp.s())
+        ns = self.ns
+        if ns == 1:
+            tp.lib.lv_sigmoid_bce_bwd_f32(P(self.logit.t), P(self.xflat), P(drec_c), P(dlogit), B, 28 * 28, 1e-12, tp.s())
+        else:
+            tp.lib.lv_sigmoid_bce_ns_bwd_f32(P(self.logit.t), P(self.xflat), P(drec_c), P(dlogit), B // ns, ns, 28 * 28, 1e-12, tp.s())
         tp.add_grad(self.logit, dlogit)
         tp.backward()
         return tp.grad_of(self.zact)

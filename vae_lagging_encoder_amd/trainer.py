@@ -857,10 +857,18 @@ class AggressiveTextTrainer(object):
 class AggressiveImageTrainer(object):
     """Fused driver for the Omniglot aggressive loop (reference image.py:295-348): one `step()` = zero_grad, VAE.loss,
     loss.mean().backward(), clip_grad_norm_(all params, 5.0), Adam step on the encoder (image.py:302-314), as a
-    stream-ordered sequence of C-ABI kernel calls with device-resident scalars (kl weight, lr, Adam step, norm)."""
+    stream-ordered sequence of C-ABI kernel calls with device-resident scalars (kl weight, lr, Adam step, norm).
+
+    nsamples = ns > 1 (image.py --nsamples: VAE.loss(x, kl_weight, nsamples=ns)): the encoder runs on the B images, ns latent samples
+    are drawn per image, the decoder runs on B*ns images in the reference's row order b*ns + s (dec_pixelcnn_v2.py:178-190; BatchNorm
+    batch statistics over all B*ns of them) reading each image's pixels from the one copy of x, and the reconstruction term of an
+    image is the mean over its samples.  read_stats() sums stay sums over the B images."""
 
     def __init__(self, vae, lr=1e-3, clip=5.0, seed=783435, device=None, precision="f32", betas=(0.9, 0.999), eps=1e-8,
-                 use_graph=False):
+                 use_graph=False, nsamples=1):
+        if isinstance(nsamples, bool) or not isinstance(nsamples, int) or nsamples < 1:
+            raise ValueError("nsamples must be an integer >= 1, not %r" % (nsamples,))
+        self.nsamples = nsamples
         self.vae = vae
         self.enc = vae.encoder._hip
         self.dec = vae.decoder._hip
@@ -957,10 +965,13 @@ class AggressiveImageTrainer(object):
         return steps
 
     def step(self, x, kl_weight, eps=None, update="encoder"):
-        """x (B,1,28,28) binarised; eps (B,1,nz) injects the reparameterisation noise (parity mode)."""
+        """x (B,1,28,28) binarised; eps (B,nsamples,nz) injects the reparameterisation noise (parity mode)."""
         d = self.device
         B = x.shape[0]
         nz = self.vae.nz
+        if eps is not None and tuple(eps.shape) != (B, self.nsamples, nz):
+            raise ValueError("eps has shape %s; this trainer (nsamples = %d) takes (%d, %d, %d)"
+                             % (tuple(eps.shape), self.nsamples, B, self.nsamples, nz))
         self.scal[0] = float(kl_weight)
         try:
             self._step(x, eps, update, d, B, nz)
@@ -975,15 +986,16 @@ class AggressiveImageTrainer(object):
             self._body(x, eps, update)
             return
         self.dec.refresh_packs(d)
-        key = (B, update, eps is None, self.vae.training)
+        ns = self.nsamples
+        key = (B, ns, update, eps is None, self.vae.training)
         st = self._static.get(key)
         if st is None:
             st = dict(x=torch.zeros(B, 1, 28, 28, dtype=torch.float32, device=d),
-                      eps=torch.zeros(B, 1, nz, dtype=torch.float32, device=d), graph=None)
+                      eps=torch.zeros(B, ns, nz, dtype=torch.float32, device=d), graph=None)
             self._static[key] = st
         st["x"].copy_(x.reshape(B, 1, 28, 28))
         if eps is not None:
-            st["eps"].copy_(eps.reshape(B, 1, nz))
+            st["eps"].copy_(eps)
         if st["graph"] is None:
             self._body(st["x"], None if eps is None else st["eps"], update)      # eager warm-up performs this call's step
             torch.cuda.synchronize(d)
@@ -1009,29 +1021,36 @@ class AggressiveImageTrainer(object):
     def _body(self, x, eps, update):
         lib, s, d = self.lib, _eng.stream_ptr(self.device), self.device
         B = x.shape[0]
-        nz = self.vae.nz
+        nz, ns = self.vae.nz, self.nsamples
         if eps is None:
-            eps = torch.empty(B, 1, nz, dtype=torch.float32, device=d)
+            eps = torch.empty(B, ns, nz, dtype=torch.float32, device=d)
             lib.lv_rng_normal_f32(P(eps), eps.numel(), P(self.rng_state), 0, s)
             lib.lv_rng_advance(P(self.rng_state), 1, s)
         mulv = self.enc.forward(x)
-        z = torch.empty(B, 1, nz, dtype=torch.float32, device=d)
+        z = torch.empty(B, ns, nz, dtype=torch.float32, device=d)
         kl = torch.empty(B, dtype=torch.float32, device=d)
-        lib.lv_reparam_kl_fwd_f32(P(mulv), P(eps), P(z), P(kl), B, 1, nz, s)
-        rec = self.dec.forward(x, z.view(B, nz))
+        lib.lv_reparam_kl_fwd_f32(P(mulv), P(eps), P(z), P(kl), B, ns, nz, s)
+        rec = self.dec.forward(x, z.view(B * ns, nz), ns)               # [B*ns], row b*ns + s
         loss = torch.empty(B, dtype=torch.float32, device=d)
         rec2 = torch.empty(B, dtype=torch.float32, device=d)
-        lib.lv_vae_loss_f32(P(rec), P(kl), self._s(0), P(loss), P(rec2), 1, B, s)
-        lib.lv_sum_accum_f32(P(loss), B, self._s(5), s)
-        lib.lv_sum_accum_f32(P(rec), B, self._s(6), s)
-        lib.lv_sum_accum_f32(P(kl), B, self._s(7), s)
         gl = torch.full((B,), 1.0 / B, dtype=torch.float32, device=d)
-        drec = torch.empty(B, dtype=torch.float32, device=d)
+        drec = torch.empty(B * ns, dtype=torch.float32, device=d)
         dkl = torch.empty(B, dtype=torch.float32, device=d)
-        lib.lv_loss_bwd_scales_f32(P(gl), None, None, self._s(0), P(drec), P(dkl), B, s)
+        if ns == 1:
+            # (lv_loss_assemble_ns_f32 sums scal[5..7] in another order than lv_sum_accum_f32: the single-sample step keeps its chain,
+            # and with it its bits)
+            lib.lv_vae_loss_f32(P(rec), P(kl), self._s(0), P(loss), P(rec2), 1, B, s)
+            lib.lv_sum_accum_f32(P(loss), B, self._s(5), s)
+            lib.lv_sum_accum_f32(P(rec), B, self._s(6), s)
+            lib.lv_sum_accum_f32(P(kl), B, self._s(7), s)
+            lib.lv_loss_bwd_scales_f32(P(gl), None, None, self._s(0), P(drec), P(dkl), B, s)
+        else:
+            # rec2[b] = mean_s rec[b*ns + s], loss[b] = rec2[b] + w*kl[b], scal[5..7] += their sums over b, and the seeds of
+            # loss.mean().backward(): drec[b*ns + s] = 1/(B*ns), dkl[b] = w/B -- one launch
+            lib.lv_loss_assemble_ns_f32(P(rec), P(kl), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(dkl), self._s(5), 1, B, ns, s)
         dz = self.dec.backward(drec)
         dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
-        lib.lv_reparam_kl_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(dmulv), B, 1, nz, s)
+        lib.lv_reparam_kl_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(dmulv), B, ns, nz, s)
         self.enc.backward(dmulv)
         ef, df = self.enc.flat, self.dec.flat
         lib.lv_sumsq_f32(P(ef.grad), ef.numel, P(self.norm_ws), self._s(2), 0, s)

@@ -209,10 +209,12 @@ class ImageTrainingLoop(object):
         weights are reloaded and BOTH Adam optimizers are re-created (moments and step counts reset, image.py:419-420);
       * the data come from shuffled DataLoaders (a fresh order for every pass, evaluation passes included), training batches
         are dynamically binarised (torch.bernoulli, image.py:287), validation / test batches are not.
-    args fields read (image.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch.
+    args fields read (image.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples (image.py --nsamples:
+    the trainer is built with it, AggressiveImageTrainer(nsamples=...), and the evaluation passes hand it to VAE.loss), test_nepoch.
 
     order_fn / binarize_fn / eps_fn inject the data order, the binarisation draw and the reparameterisation noise (parity replays
-    of a recorded reference run); the defaults draw them as the reference's CPU path does / on the device."""
+    of a recorded reference run); the defaults draw them as the reference's CPU path does / on the device.  eps_fn(x) returns
+    eps [B][nsamples][nz].  A `trainer` that is handed in must have been built with the same nsamples as args'."""
 
     CLIP_GRAD, DECAY_EPOCH, LR_DECAY, MAX_DECAY, LR0 = 5.0, 20, 0.5, 5, 0.001          # image.py:18-21, 267-269
 
@@ -224,7 +226,11 @@ class ImageTrainingLoop(object):
         self.train_loader = ShuffledLoader(x_train, args.batch_size, order_fn)
         self.val_loader = ShuffledLoader(x_val, args.batch_size, order_fn)
         self.test_loader = ShuffledLoader(x_test, args.batch_size, order_fn) if x_test is not None else None
-        self.trainer = trainer if trainer is not None else AggressiveImageTrainer(vae, lr=self.LR0, clip=self.CLIP_GRAD, seed=seed)
+        self.nsamples = int(getattr(args, "nsamples", 1))
+        if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
+            raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
+        self.trainer = trainer if trainer is not None else AggressiveImageTrainer(vae, lr=self.LR0, clip=self.CLIP_GRAD, seed=seed,
+                                                                                  nsamples=self.nsamples)
         self.rng = np_rng if np_rng is not None else np.random
         self.binarize_fn, self.eps_fn, self.epoch_hook = binarize_fn, eps_fn, epoch_hook
         self.decay_epoch = self.DECAY_EPOCH if decay_epoch is None else decay_epoch
