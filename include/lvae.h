@@ -653,6 +653,22 @@ int lv_beam_advance_f32(const float* pick_score, const int* pick_flat, const flo
 int lv_beam_backtrace(const float* score, const int* meta, const float* done_score, const int* done_ref, const int* trace,
                       int64_t* ids, int* len, float* win_score, int B, int K, int Tmax, int start_tok, void* stream);
 
+/* Device-resident greedy / sample decoding for the LSTM decoder (lv_rollout.hip; dec_lstm.py:270-367 for n sentences at once).
+ * State of n rows in caller-owned buffers: tok int64 [n] (next input word), alive int32 [n], ids int64 [n][Tmax] (emitted words),
+ * len int32 [n], score f32 [n] (running log-probability), margin f32 [n] (greedy: smallest top-1 minus top-2 logit gap so far),
+ * counter int32 [1] (rows still alive), h / c as two [n][H] halves (the cell reads one and writes the other).
+ * init: tok = start_tok, alive = 1, len = 0, score = 0, margin = +inf, counter = n, (h0, c0) copied into (h, c). */
+int lv_rollout_init_f32(const float* h0, const float* c0, float* h, float* c, int64_t* tok, int* alive, int* len, float* score,
+                        float* margin, int* counter, int n, int H, int V, int start_tok, void* stream);
+/* step t (0-based, < Tmax) in one launch.  The pick from logits [n][ld]: u == NULL -> argmax, bit-equal to lv_argmax_rows_f32 (rows
+ * 16-byte aligned, LV_ERR_ALIGN otherwise); else the inverse-CDF draw with u [n], bit-equal to lv_sample_rows_f32 (margin may then
+ * be NULL).  A live row: ids[r][t] = tok[r] = pick, len += 1, score += (x[pick] - M) - log S, margin = min(margin, top1 - top2)
+ * (greedy), alive = (pick != end_tok), counter drops by one per row that ended.  A dead row keeps ids / len / score / margin / tok.
+ * Every row's state moves (h_src, c_src) -> (h_dst, c_dst) (different halves).  counter == 0 on entry: nothing is changed. */
+int lv_rollout_pick_f32(const float* logits, long ld, const float* u, const float* h_src, const float* c_src, float* h_dst,
+                        float* c_dst, int64_t* tok, int* alive, int64_t* ids, int* len, float* score, float* margin,
+                        int* counter, int t, int Tmax, int n, int H, int V, int end_tok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

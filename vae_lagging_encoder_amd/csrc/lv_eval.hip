@@ -8,15 +8,9 @@
 // pieces below are what the reference computes on top of them with broadcasting tensor algebra -- here one launch each,
 // no (z_batch, x_batch, nz) or (batch, nsamples, nz) temporaries.
 #include "lv_device.h"
+#include "lv_pick.h"
 
 namespace {
-
-__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    if (mn == -INFINITY) { m = mn; s = 0.f; return; }
-    s = s * expf(m - mn) + s2 * expf(m2 - mn);
-    m = mn;
-}
 
 constexpr float LOG_2PI = 1.8378770664093453f;
 
@@ -50,11 +44,11 @@ __global__ __launch_bounds__(256) void logsumexp_rows_kernel(const float* __rest
     const int l = (int)threadIdx.x & 63;
     if (r >= R) return;
     float m = -INFINITY, s = 0.f;
-    for (int c = l; c < C; c += 64) lse_merge(m, s, in[(long)r * ld + c], 1.f);
+    for (int c = l; c < C; c += 64) lv_lse_merge(m, s, in[(long)r * ld + c], 1.f);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float m2 = __shfl_xor(m, d, 64), s2 = __shfl_xor(s, d, 64);
-        lse_merge(m, s, m2, s2);
+        lv_lse_merge(m, s, m2, s2);
     }
     if (l == 0) out[r] = m + logf(s) + add;
 }
@@ -77,12 +71,12 @@ __global__ __launch_bounds__(256) void mi_logqz_kernel(const float* __restrict__
             q += d * d / expf(lj[k]);
             sl += lj[k];
         }
-        lse_merge(m, s, -0.5f * q - 0.5f * ((float)nz * LOG_2PI + sl), 1.f);
+        lv_lse_merge(m, s, -0.5f * q - 0.5f * ((float)nz * LOG_2PI + sl), 1.f);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float m2 = __shfl_xor(m, d, 64), s2 = __shfl_xor(s, d, 64);
-        lse_merge(m, s, m2, s2);
+        lv_lse_merge(m, s, m2, s2);
     }
     if (l == 0) log_qz[i] = m + logf(s) - logf((float)Bx);
 }
@@ -180,18 +174,18 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     const int l = (int)threadIdx.x & 63;
     if (r >= R) return;
     float best = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = LV_ARGMAX_NONE;
     for (int c = l; c < C; c += 64) {
         const float v = in[(long)r * ld + c];
-        if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+        if (lv_argmax_before(v, c, best, bi)) { best = v; bi = c; }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float ob = __shfl_xor(best, d, 64);
         const int oi = __shfl_xor(bi, d, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (lv_argmax_before(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
-    if (l == 0) idx[r] = bi == 0x7fffffff ? 0 : bi;
+    if (l == 0) idx[r] = bi == LV_ARGMAX_NONE ? 0 : bi;
 }
 
 // out[r][c] = in[r][c] - logsumexp_c in[r][:]  (+ addrow[r]): F.log_softmax (+ the hypothesis' running log-probability)
@@ -200,67 +194,30 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* __re
     __shared__ float sm[4], ss[4];
     const int r = (int)blockIdx.x, tid = (int)threadIdx.x, l = tid & 63, w = tid >> 6;
     float m = -INFINITY, s = 0.f;
-    for (int c = tid; c < C; c += 256) lse_merge(m, s, in[(long)r * ld + c], 1.f);
+    for (int c = tid; c < C; c += 256) lv_lse_merge(m, s, in[(long)r * ld + c], 1.f);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const float m2 = __shfl_xor(m, d, 64), s2 = __shfl_xor(s, d, 64);
-        lse_merge(m, s, m2, s2);
+        lv_lse_merge(m, s, m2, s2);
     }
     if (l == 0) { sm[w] = m; ss[w] = s; }
     __syncthreads();
     float M = sm[0], S = ss[0];
-    for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
+    for (int i = 1; i < 4; ++i) lv_lse_merge(M, S, sm[i], ss[i]);
     // (x - M) - log S, not x - (M + log S): the sum M + log S is rounded at the magnitude of the logits (half an ulp of M), which a
     // common offset of the row makes arbitrarily larger than the result; x - M is rounded at the magnitude of the difference
     const float lz = logf(S) - (addrow ? addrow[r] : 0.f);
     for (int c = tid; c < C; c += 256) out[(long)r * ldo + c] = (in[(long)r * ld + c] - M) - lz;
 }
 
-// categorical draw from softmax(in[r][:]) by inverse CDF with the uniform u[r] in [0,1): single wave per row, two passes
-// (logsumexp, then a blocked running sum).  With w[c] = exp(in[r][c] - max) and s = sum_c w[c]: idx[r] = the first column with
-// w[c] > 0 whose inclusive running sum reaches u*s.  A column of weight zero (-inf logit, or underflow) is never returned, as
-// torch.multinomial never returns an index of probability zero: when rounding leaves the f32 running sum short of u*s (u close
-// to 1), idx[r] is the LAST column with positive weight; C - 1 is returned only if no column has positive weight.
+// categorical draw from softmax(in[r][:]) by inverse CDF with the uniform u[r] in [0,1): single wave per row; the rule (zero-weight
+// columns, a running sum that rounding leaves short) is lv_wave_sample_row's (lv_pick.h)
 __global__ __launch_bounds__(64) void sample_rows_kernel(const float* __restrict__ in, long ld, int R, int C,
                                                          const float* __restrict__ u, int64_t* __restrict__ idx) {
     const int r = (int)blockIdx.x, l = (int)threadIdx.x;
-    float m = -INFINITY, s = 0.f;
-    for (int c = l; c < C; c += 64) lse_merge(m, s, in[(long)r * ld + c], 1.f);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const float m2 = __shfl_xor(m, d, 64), s2 = __shfl_xor(s, d, 64);
-        lse_merge(m, s, m2, s2);
-    }
-    const float target = u[r] * s;                     // in units of exp(x - m)
-    float run = 0.f;
-    int found = -1;
-    int last_pos = -1;                                 // highest column with positive weight seen so far: the fallback
-    bool done = false;
-    for (int c0 = 0; c0 < C && !done; c0 += 64) {      // blocks of 64 consecutive columns, inclusive scan inside the wave
-        const int c = c0 + l;
-        float p = c < C ? expf(in[(long)r * ld + c] - m) : 0.f;
-        float sc = p;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const float o = __shfl_up(sc, d, 64);
-            if (l >= d) sc += o;
-        }
-        const bool hit = p > 0.f && run + sc >= target;      // p > 0 implies c < C
-        // lowest lane that hit, highest lane with positive weight
-        int first = hit ? l : 64;
-        int pos = p > 0.f ? c : -1;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int o = __shfl_xor(first, d, 64);
-            first = o < first ? o : first;
-            const int q = __shfl_xor(pos, d, 64);
-            pos = q > pos ? q : pos;
-        }
-        if (first < 64) { found = c0 + first; done = true; }
-        last_pos = pos > last_pos ? pos : last_pos;
-        run += __shfl(sc, 63, 64);
-    }
-    if (l == 0) idx[r] = found >= 0 ? found : (last_pos >= 0 ? last_pos : C - 1);
+    float m, s;
+    const int pick = lv_wave_sample_row(in + (long)r * ld, C, u[r], l, m, s);
+    if (l == 0) idx[r] = pick;
 }
 
 }  // namespace

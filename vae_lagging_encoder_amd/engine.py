@@ -1907,3 +1907,84 @@ class LSTMBeamSearcher(object):
         info = {"score": fl[:, 0].copy(), "steps": meta[:, 2].copy(), "n_completed": meta[:, 0].copy(),
                 "min_margin": fl[:, 1].copy()}
         return ids, info
+
+
+class LSTMRollout(object):
+    """Greedy / sample decoding for all sentences of a batch with every per-step decision on the device (lv_rollout.hip;
+    reference modules/decoders/dec_lstm.py:270-367, whose loop -- like LSTMDecoder._roll_out -- masks on the host and reads
+    "anybody alive" once per word).
+
+    n sentences are n rows of LSTMDecodeStepper's exact-f32 launch sequence.  The z-projection (+ biases) of a row never changes,
+    so it is computed once per call into Zp; a step is five launches: embedding gather of `tok`, input product with Zp as its
+    addend, the T = 1 cell (reads half 0 of the (h, c) workspace, writes half 1), the vocabulary product, and
+    lv_rollout_pick_f32, which picks, keeps ids / len / score / margin / alive, and moves the state back into half 0 -- no
+    clone() / copy_() per step.  The host reads the one-int alive counter every `poll` steps and stops queueing when it is zero;
+    steps queued past that point are no-ops by the kernel's counter gate, so the result does not depend on `poll`.
+
+    Sampling draws torch.rand(n, generator=...) per queued step: the call LSTMDecoder._roll_out makes, in the same order, so for a
+    given generator state both routes pick from the same uniforms.  The one difference: up to poll - 1 further draws are consumed
+    after the last sentence has ended."""
+
+    TMAX = 99                                                        # the reference's `length_c < 100`
+
+    def __init__(self, stepper, poll=8):
+        self.st = stepper
+        self.device = stepper.device
+        self.poll = poll
+        self.ws = {}
+
+    def _w(self, n):
+        w = self.ws.get(n)
+        if w is None:
+            d, T = self.device, self.TMAX
+            w = _NS()
+            w.tok = torch.empty(n, dtype=torch.int64, device=d)
+            w.alive = torch.empty(n, dtype=torch.int32, device=d)
+            w.ids = torch.zeros(n, T, dtype=torch.int64, device=d)
+            w.len = torch.empty(n, dtype=torch.int32, device=d)
+            w.score = torch.empty(n, dtype=torch.float32, device=d)
+            w.margin = torch.empty(n, dtype=torch.float32, device=d)
+            w.counter = torch.empty(1, dtype=torch.int32, device=d)
+            self.ws[n] = w
+        return w
+
+    def decode(self, z2, start_tok, end_tok, sample=False, generator=None):
+        """z2 [n][nz] -> (ids: list of n int lists without <s>, info: dict of numpy arrays score / steps and, for greedy,
+        min_margin, one entry per sentence)."""
+        st = self.st
+        n = z2.shape[0]
+        h0, c0 = st.init_state(z2)                                   # refreshes the stepper's view of the parameters
+        V, ni, H, nz = st.eng.dims()
+        v = st.eng.flat.views
+        lib, s = st.lib, stream_ptr(self.device)
+        T = self.TMAX
+        w, sw = self._w(n), st._w(n)
+        lib.lv_rollout_init_f32(P(h0), P(c0), P(sw.hs), P(sw.cs), P(w.tok), P(w.alive), P(w.len), P(w.score), P(w.margin),
+                                P(w.counter), n, H, V, start_tok, s)
+        zr = z2.contiguous().float()
+        wih = v["lstm.weight_ih_l0"]
+        _gemm(lib, s, 0, 1, n, 4 * H, nz, P(zr), nz, P(wih, ni), ni + nz, P(sw.Zp), 4 * H,
+              add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
+        poll = max(1, int(self.poll))
+        for t in range(T):
+            lib.lv_embed_gather_f32(P(v["embed.weight"]), P(w.tok), 1, None, 1.0, P(sw.X), 1, n, ni, V, s)
+            _gemm(lib, s, 0, 1, n, 4 * H, ni, P(sw.X), ni, P(wih), ni + nz, P(sw.Gx), 4 * H, add1=P(sw.Zp), ld1=4 * H, mod1=n)
+            lib.lv_lstm_fwd_f32(P(sw.Gx), P(v["lstm.weight_hh_l0"]), P(sw.hs), P(sw.cs), P(sw.gates), None, 1.0, None,
+                                P(sw.lstm_ws), 1, n, H, s)
+            _gemm(lib, s, 0, 1, n, V, H, P(sw.hs, n * H), H, P(v["pred_linear.weight"]), H, P(sw.logits), sw.ldl)
+            u = torch.rand(n, device=self.device, generator=generator) if sample else None
+            lib.lv_rollout_pick_f32(P(sw.logits), sw.ldl, P(u), P(sw.hs, n * H), P(sw.cs, n * H), P(sw.hs), P(sw.cs), P(w.tok),
+                                    P(w.alive), P(w.ids), P(w.len), P(w.score), P(w.margin), P(w.counter), t, T, n, H, V,
+                                    end_tok, s)
+            if (t + 1) % poll == 0 and t + 1 < T and int(w.counter.item()) == 0:      # the only host read of the loop
+                break
+        # one device-to-host copy: ids | len | the bits of (score, min margin)
+        out = torch.cat((w.ids, w.len.to(torch.int64).unsqueeze(1),
+                         torch.stack((w.score, w.margin), dim=1).view(torch.int32).to(torch.int64)), dim=1).cpu()
+        lens = out[:, T].tolist()
+        ids = [row[:m] for row, m in zip(out[:, :T].tolist(), lens)]
+        fl = out[:, T + 1:].to(torch.int32).contiguous().view(torch.float32).numpy()
+        info = {"score": fl[:, 0].copy(), "steps": out[:, T].numpy().copy()}
+        if not sample:
+            info["min_margin"] = fl[:, 1].copy()
+        return ids, info

@@ -5,8 +5,9 @@ Same constructor, containers, construction order and state_dict keys (`embed.wei
 embedding gather fused with dropout_in, z-projection folded into the input GEMM epilogue (the cat((embed, z)) is
 never materialised), fused LSTM step kernels with dropout_out in the epilogue, f32 MFMA vocabulary projection,
 row softmax-NLL; hand-written backward.  Generation (beam / greedy / sample decoding, reference lines 163-367;
-SURVEY.md 8f row 4) steps the same kernels one token at a time through engine.LSTMDecodeStepper; beam search decodes the
-whole batch together, every decision on the device, through engine.LSTMBeamSearcher (csrc/lv_beam.hip).
+SURVEY.md 8f row 4) steps the same kernels one token at a time through engine.LSTMDecodeStepper; every strategy decodes the
+whole batch together with every decision on the device: beam search through engine.LSTMBeamSearcher (csrc/lv_beam.hip), greedy
+and sample decoding through engine.LSTMRollout (csrc/lv_rollout.hip).
 """
 import numpy as np
 import torch
@@ -159,18 +160,66 @@ class LSTMDecoder(DecoderBase):
         keep = torch.stack(masks, dim=1).cpu().tolist()
         return [[self.vocab.id2word(w) for w, k in zip(row, krow) if k] for row, krow in zip(ids, keep)]
 
-    def greedy_decode(self, z):
-        """Greedy decoding from z (batch_size, nz) -> list of word lists (reference dec_lstm.py:270-318)."""
-        return self._roll_out(z, lambda st, logits: st.argmax(logits))
+    # True: greedy_decode / sample_decode keep the whole loop on the device through engine.LSTMRollout (lv_rollout.hip); False
+    # selects _roll_out above, one host decision per word (A/B runs, the tests' reference)
+    batched_rollout = True
+    rollout_poll = 8             # steps between the device route's reads of the "sentences still alive" counter
 
-    def sample_decode(self, z, generator=None):
+    def _rollout(self, device):
+        st = self._stepper(device)
+        ro = getattr(self, "_ro", None)
+        if ro is None or ro.st is not st:
+            ro = self._ro = _eng.LSTMRollout(st)
+        ro.poll = self.rollout_poll
+        return ro
+
+    def _decode_loop(self, z, pick, sample, generator, return_info):
+        batch_size = z.size(0)
+        if self.batched_rollout and batch_size > 0:
+            with torch.no_grad():
+                ids, info = self._rollout(z.device).decode(z.reshape(batch_size, -1).float(), self.vocab["<s>"], self.vocab["</s>"],
+                                                            sample=sample, generator=generator)
+            decoded = [[self.vocab.id2word(w) for w in row] for row in ids]
+            return (decoded, info) if return_info else decoded
+        if not return_info:
+            return self._roll_out(z, pick)
+        # the per-step route with the same per-sentence quantities, from the stepper's helpers
+        rec = {"lp": [], "gap": []}
+
+        def recording_pick(st, logits):
+            tok = pick(st, logits)
+            rec["lp"].append(st.log_softmax(logits).gather(1, tok.view(-1, 1)).view(-1))
+            if not sample:
+                top = torch.topk(logits, min(2, logits.shape[1]), dim=1)[0]
+                rec["gap"].append(top[:, 0] - top[:, -1] if top.shape[1] > 1 else torch.full_like(top[:, 0], float("inf")))
+            return tok
+        decoded = self._roll_out(z, recording_pick)
+        steps = np.asarray([len(s) for s in decoded], dtype=np.int64)
+        live = torch.arange(len(rec["lp"])).view(1, -1) < torch.from_numpy(steps).view(-1, 1)      # [n][steps queued]
+        lp = torch.stack(rec["lp"], dim=1).cpu()
+        info = {"score": torch.where(live, lp, torch.zeros_like(lp)).sum(dim=1).numpy().astype(np.float32), "steps": steps}
+        if not sample:
+            gap = torch.stack(rec["gap"], dim=1).cpu()
+            info["min_margin"] = torch.where(live, gap, torch.full_like(gap, float("inf"))).min(dim=1)[0].numpy().astype(np.float32)
+        return decoded, info
+
+    def greedy_decode(self, z, return_info=False):
+        """Greedy decoding from z (batch_size, nz) -> list of word lists (reference dec_lstm.py:270-318): no <s>, </s> included
+        when emitted, at most 99 words.  return_info=True also returns a dict of per-sentence numpy arrays: `score`
+        (log p(words | z)), `steps` (words emitted), `min_margin` (smallest top-1 minus top-2 logit gap over the sentence's
+        steps)."""
+        return self._decode_loop(z, lambda st, logits: st.argmax(logits), False, None, return_info)
+
+    def sample_decode(self, z, generator=None, return_info=False):
         """Ancestral sampling from z (reference dec_lstm.py:320-367).  The categorical draw is an inverse-CDF pick from a device
-        uniform (torch.rand; `generator` makes it reproducible) instead of torch.multinomial's sampler: same distribution,
-        different stream."""
+        uniform (torch.rand, one call of batch_size values per step; `generator` makes it reproducible) instead of
+        torch.multinomial's sampler: same distribution, different stream.  Both routes draw the same uniforms in the same order;
+        the device route consumes up to rollout_poll - 1 further draws after the last sentence has ended.  return_info=True also
+        returns `score` and `steps` per sentence."""
         def pick(st, logits):
             u = torch.rand(logits.shape[0], device=logits.device, generator=generator)
             return st.sample(logits, u)
-        return self._roll_out(z, pick)
+        return self._decode_loop(z, pick, True, generator, return_info)
 
     # True: beam_search_decode decodes the whole batch together through engine.LSTMBeamSearcher (lv_beam.hip) when the shape is
     # inside its envelope; False forces the sentence-by-sentence route below (A/B runs, tests)

@@ -102,13 +102,14 @@ class VAE(nn.Module):
 
     # ---- generation (delegated; generation itself is outside the hot path) -----------------------------
     def decode(self, z, strategy, K=5, return_info=False):
-        """return_info (beam only): also the per-sentence dict LSTMDecoder.beam_search_decode(..., return_info=True) returns."""
+        """return_info: also the per-sentence dict the decoder's beam_search_decode / greedy_decode / sample_decode returns with
+        return_info=True."""
         if strategy not in _GENERATORS:
             raise ValueError("the decoding strategy is not supported")
         fn = getattr(self.decoder, _GENERATORS[strategy])
         if strategy == "beam":
             return fn(z, K, return_info=True) if return_info else fn(z, K)
-        return fn(z)
+        return fn(z, return_info=True) if return_info else fn(z)
 
     def reconstruct(self, x, decoding_strategy="greedy", K=5):
         return self.decode(self.sample_from_inference(x).squeeze(1), decoding_strategy, K)
