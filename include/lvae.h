@@ -482,6 +482,34 @@ int lv_dec_cond_ll_f32(const int64_t* x, int B, int T, const float* z, long z_st
 int lv_grid_posterior_f32(const float* cond_ll, const float* z, long z_stride, int B, int K, int nz, float* log_post,
                           float* mean, void* stream);
 
+/* ---- Metropolis-Hastings sampling from the model posterior (lv_mh.hip): VAE.sample_from_posterior (modules/vae.py:218-254).
+ * A random-walk chain per (sentence, chain): next = eps * std + cur (two roundings), ratio = log p(next, x) - log p(cur, x),
+ * accept = ratio >= 0 || u < exp(ratio) (a NaN ratio rejects), cur / cur_ll selected, never blended.  State in caller-owned
+ * buffers: cur [B][C][nz], cur_ll [B][C], accepts [B][C] (int32 acceptance counts); samples [B][nsamples][C][nz]; iteration i
+ * (counted from 0 over the whole chain) stores kept sample (i - burn_in) / thin when i >= burn_in and thin divides i - burn_in.
+ * ratio_out / accept_out (float / int32, one per chain and iteration) may be NULL.  The kernels hold no generator: eps and u
+ * are buffers of standard normal / uniform [0, 1) draws.
+ * lv_mh_chain_f32 (vae.py:218-254): the fused route for the eval-mode LSTM decoder inside lv_dec_cond_ll_f32's envelope
+ * (lv_mh_chain_f32_supported: the same answer) -- n_iter iterations iter0 .. iter0 + n_iter - 1 in one launch, one workgroup per
+ * (sentence, 16 chains); eps [n_iter][B][C][nz], u [n_iter][B][C]; first != 0: score the starting point in cur first (incoming
+ * cur_ll / accepts ignored, counts start at 0).  ws: lv_mh_chain_f32_ws_floats floats, 16-byte aligned, filled ONCE per chain by
+ * lv_mh_chain_prep_f32 (weights as the module stores them; vae.py:218-254's x and decoder). */
+int lv_mh_chain_f32_supported(int V, int ni, int H, int nz, int T);
+long lv_mh_chain_f32_ws_floats(int V, int H, int nz, int B, int T);
+int lv_mh_chain_prep_f32(const int64_t* x, int B, int T, const float* embed, const float* trans, const float* w_ih,
+                         const float* w_hh, const float* b_ih, const float* b_hh, const float* pred, int V, int ni, int H, int nz,
+                         float* ws, void* stream);
+int lv_mh_chain_f32(const int64_t* x, int B, int T, const float* ws, int V, int H, int nz, int C, float* cur, float* cur_ll,
+                    int* accepts, const float* eps, const float* u, int n_iter, int iter0, int burn_in, int thin, int nsamples,
+                    float std, int first, float* samples, float* ratio_out, int* accept_out, void* stream);
+/* lv_mh_step_f32 (vae.py:218-254, one pass of the loop at 232-251): the propose / accept glue for any decoder, rows = B * C
+ * chains, any nz >= 1.  cond_ll [rows] = log p(x|prop) as eval_cond_ll returned it; prop [rows][nz] is replaced by the next
+ * iteration's proposals eps_next * std + cur (eps_next NULL: left alone); keep = index of the kept sample this iteration
+ * produces or -1.  init != 0 (vae.py:227-228): cond_ll was computed at cur -- cur_ll = log p(cur, x), accepts = 0, first proposals. */
+int lv_mh_step_f32(const float* cond_ll, float* prop, float* cur, float* cur_ll, int* accepts, const float* u,
+                   const float* eps_next, float std, float* samples, int rows, int C, int nz, int nsamples, int keep, int init,
+                   float* ratio_out, int* accept_out, void* stream);
+
 /* ---- generation helpers (lv_eval.hip; SURVEY.md 8f row 4: modules/decoders/dec_lstm.py:163-367) -------------------------
  * torch.argmax(logits, dim=1) (greedy_decode, dec_lstm.py:304): lowest index among equal maxima */
 int lv_argmax_rows_f32(const float* in, long ld, int R, int C, int64_t* idx, void* stream);

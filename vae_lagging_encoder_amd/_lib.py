@@ -188,6 +188,11 @@ SIGNATURES = {
     "lv_dec_cond_ll_f32_ws_floats": [_i, _i, _i, _i, _i],
     "lv_dec_cond_ll_f32": [_vp, _i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "lv_grid_posterior_f32": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp],
+    "lv_mh_chain_f32_supported": [_i, _i, _i, _i, _i],
+    "lv_mh_chain_f32_ws_floats": [_i, _i, _i, _i, _i],
+    "lv_mh_chain_prep_f32": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "lv_mh_chain_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
+    "lv_mh_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "lv_beam_supported": [_i, _i, _i],
     "lv_beam_ws_floats": [_i, _i, _i],
     "lv_beam_init_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -200,7 +205,8 @@ SIGNATURES = {
 
 
 _LONG_FNS = ("lv_lstm_ws_floats", "lv_conv1x1_wgrad_ws_floats", "lv_conv1x1_blocks", "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats", "lv_conv32_wpack_floats",
-             "lv_conv32_wgrad_ws_floats", "lv_dec_cond_ll_f32_ws_floats", "lv_beam_ws_floats", "lv_bn_partial_floats")
+             "lv_conv32_wgrad_ws_floats", "lv_dec_cond_ll_f32_ws_floats", "lv_beam_ws_floats", "lv_bn_partial_floats",
+             "lv_mh_chain_f32_ws_floats")
 
 
 class LvaeError(RuntimeError):
@@ -230,7 +236,8 @@ class Lib(object):
                            "lv_conv32_wgrad_slabs", "lv_conv32_wgrad_ws_floats", "lv_conv32_wgrad_parts", "lv_conv1x1_wgrad_parts", "lv_conv32_blocks", "lv_conv1x1_blocks", "lv_conv1x1_wgrad_ws_floats", "lv_sumsq_workspace_floats", "lv_lstm_ws_floats", "lv_bn_workspace_floats",
                            "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats",
                            "lv_pixelcnn_net_words", "lv_pixelcnn_block_words", "lv_conv32_tap_split", "lv_dec_cond_ll_f32_supported",
-                           "lv_dec_cond_ll_f32_ws_floats", "lv_beam_supported", "lv_beam_ws_floats", "lv_bn_partial_floats"}
+                           "lv_dec_cond_ll_f32_ws_floats", "lv_beam_supported", "lv_beam_ws_floats", "lv_bn_partial_floats",
+                           "lv_mh_chain_f32_supported", "lv_mh_chain_f32_ws_floats"}
 
     def __getattr__(self, name):
         if name.startswith("lv_"):

@@ -1526,6 +1526,69 @@ class LSTMDecoderEngine(object):
                                     stream_ptr(device))
         return out
 
+    @staticmethod
+    def mh_default_iters_per_launch(T):
+        """The largest n with n * (T - 1) <= 2048 decoder timesteps in one launch, at least 1 (a launch stays short on a
+        shared device; see LSTMDecoderEngine.mh_chain)."""
+        return max(1, 2048 // max(1, int(T) - 1))
+
+    def mh_chain(self, x, z0, draw, burn_in, thin, nsamples, std, iters_per_launch=None):
+        """Random-walk Metropolis-Hastings chains on p(z|x) (VAE.sample_from_posterior, reference vae.py:218-254) through
+        lv_mh_chain_f32: x int64 [B][T], starting points z0 [B][C][nz] (C independent chains per sentence), burn_in +
+        nsamples * thin iterations.  draw(i0, n) -> (eps [n][B][C][nz], u [n][B][C]) hands over the noise of iterations
+        i0 .. i0 + n - 1.  The weight images and the per-sentence input projection are prepared once; the chain then runs in
+        launches of at most iters_per_launch iterations (default: mh_default_iters_per_launch(T)) whose cut does not change
+        the result.  The caller checks cond_ll_supported().  Every operand must live on x's device: a mismatch is refused
+        before anything is launched.  Nothing is read back to the host.
+        -> dict(samples [B][nsamples][C][nz], cur, log_joint [B][C], accepts [B][C] int32, ratios / flags [iterations][B][C])."""
+        device = x.device
+        if z0.device != device:
+            raise _lib.LvaeError("mh_chain: z0 is on %s, x on %s" % (z0.device, device))
+        self.ensure(device)
+        V, ni, H, nz = self.dims()
+        if x.dim() != 2 or x.dtype != torch.int64 or z0.dim() != 3 or z0.shape[0] != x.shape[0] or z0.shape[2] != nz:
+            raise ValueError("mh_chain: x int64 [B][T] and z0 [B][C][%d] expected, got %s %s and %s"
+                             % (nz, x.dtype, tuple(x.shape), tuple(z0.shape)))
+        burn_in, thin, nsamples = int(burn_in), int(thin), int(nsamples)
+        if burn_in < 0 or thin < 1 or nsamples < 1:
+            raise ValueError("mh_chain: burn_in >= 0, thin >= 1, nsamples >= 1 expected")
+        B, T = x.shape
+        C = z0.shape[1]
+        total = burn_in + nsamples * thin
+        per = self.mh_default_iters_per_launch(T) if iters_per_launch is None else int(iters_per_launch)
+        if per < 1:
+            raise ValueError("mh_chain: iters_per_launch >= 1 expected")
+        # every chunk's noise is fetched (and checked) before the first launch
+        chunks = []
+        for i0 in range(0, total, per):
+            n = min(per, total - i0)
+            eps, u = draw(i0, n)
+            if eps.device != device or u.device != device:
+                raise _lib.LvaeError("mh_chain: noise is on %s / %s, x on %s" % (eps.device, u.device, device))
+            if tuple(eps.shape) != (n, B, C, nz) or tuple(u.shape) != (n, B, C):
+                raise ValueError("mh_chain: eps [%d][%d][%d][%d] and u [%d][%d][%d] expected, got %s and %s"
+                                 % (n, B, C, nz, n, B, C, tuple(eps.shape), tuple(u.shape)))
+            chunks.append((i0, n, eps.contiguous().float(), u.contiguous().float()))
+        x = x.contiguous()
+        v = self.flat.views
+        s = stream_ptr(device)
+        f32 = dict(dtype=torch.float32, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        ws = torch.empty(self.lib.lv_mh_chain_f32_ws_floats(V, H, nz, B, T), **f32)
+        cur = z0.detach().float().contiguous().clone()
+        cur_ll, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **i32)
+        samples = torch.empty(B, nsamples, C, nz, **f32)
+        ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32)
+        self.lib.lv_mh_chain_prep_f32(P(x), B, T, P(v["embed.weight"]), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]),
+                                      P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]),
+                                      P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), s)
+        for i0, n, eps, u in chunks:
+            self.lib.lv_mh_chain_f32(P(x), B, T, P(ws), V, H, nz, C, P(cur), P(cur_ll), P(accepts), P(eps), P(u), n, i0, burn_in,
+                                     thin, nsamples, float(std), 1 if i0 == 0 else 0, P(samples), P(ratios, i0 * B * C),
+                                     P(flags, i0 * B * C), s)
+        return {"samples": samples, "cur": cur, "log_joint": cur_ll, "accepts": accepts, "ratios": ratios, "flags": flags,
+                "iterations": total}
+
     def backward(self, drec, gen=None, partial_dz=False):
         """drec [B*ns] = dL/d rec of every decoder row -> fills self.flat.grad; returns dz [B*ns][nz] (partial_dz: the tail kernel's
         partial sums [parts][B*ns][nz] and their count instead).  ns > 1: the gate gradients are summed over a
@@ -1702,6 +1765,38 @@ def grid_posterior(cond_ll, z, want_log_post=True):
     mean = torch.empty(B, nz, dtype=torch.float32, device=cond_ll.device)
     lib.lv_grid_posterior_f32(P(cond_ll), P(z), 0 if z.dim() == 2 else K * nz, B, K, nz, P(log_post), P(mean), s)
     return log_post, mean
+
+
+def mh_step(cond_ll, prop, cur, cur_ll, accepts, u, eps_next, std, samples, keep, init=False, ratio_out=None, flag_out=None):
+    """One launch of lv_mh_step_f32, the propose / accept glue of VAE.sample_from_posterior (reference vae.py:218-254) for any
+    decoder: cond_ll [B][C] = log p(x|prop) as eval_cond_ll returned it; prop, cur [B][C][nz], cur_ll [B][C] f32 and accepts
+    [B][C] int32 are updated in place (prop becomes the next proposals eps_next * std + cur; eps_next None: left alone);
+    samples [B][nsamples][C][nz] takes cur at index keep (-1: nothing stored); init: cond_ll was computed at cur -- score the
+    starting point, zero the counts, write the first proposals.  Every operand on one device, contiguous, or it is refused
+    before the launch."""
+    device = cond_ll.device
+    ops = {"prop": prop, "cur": cur, "cur_ll": cur_ll, "accepts": accepts, "u": u, "eps_next": eps_next, "samples": samples,
+           "ratio_out": ratio_out, "flag_out": flag_out}
+    for name, t in ops.items():
+        if t is None:
+            continue
+        if t.device != device:
+            raise _lib.LvaeError("mh_step: %s is on %s, cond_ll on %s" % (name, t.device, device))
+        want = torch.int32 if name in ("accepts", "flag_out") else torch.float32
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError("mh_step: %s must be a contiguous %s tensor" % (name, want))
+    lib, s = backend_for(device), stream_ptr(device)
+    B, C, nz = cur.shape
+    rows = B * C
+    cond = cond_ll.detach().contiguous().float()
+    nsamples = samples.shape[1]
+    if (cond.numel() != rows or tuple(prop.shape) != (B, C, nz) or cur_ll.numel() != rows or accepts.numel() != rows
+            or tuple(samples.shape) != (B, nsamples, C, nz) or (u is not None and u.numel() != rows)
+            or (eps_next is not None and eps_next.numel() != rows * nz)
+            or (ratio_out is not None and ratio_out.numel() != rows) or (flag_out is not None and flag_out.numel() != rows)):
+        raise ValueError("mh_step: operand shapes do not match cur %s" % (tuple(cur.shape),))
+    lib.lv_mh_step_f32(P(cond), P(prop), P(cur), P(cur_ll), P(accepts), P(u), P(eps_next), float(std), P(samples), rows, C, nz,
+                       nsamples, int(keep), 1 if init else 0, P(ratio_out), P(flag_out), s)
 
 
 def calc_mi(mu, logvar, z):

@@ -193,6 +193,139 @@ class VAE(nn.Module):
         w = self.eval_log_model_posterior(x, grid_z).exp()
         return (w.unsqueeze(2) * grid_z.unsqueeze(0)).sum(1)
 
+    # True: sample_from_posterior takes the fused chain kernel (lv_mh_chain_f32) where _fused_mh_ok allows it; False forces
+    # the per-iteration route (A/B runs, tests)
+    fused_mh = True
+
+    def _fused_mh_ok(self, x, z0):
+        """Route "chain" of sample_from_posterior, in the spirit of _fused_grid_ok: an LSTM decoder inside lv_mh_chain_f32's
+        envelope that draws no dropout mask (not training, or both p are 0), x a 2-D int64 tensor, everything on one device
+        the package has kernels for."""
+        dec = self.decoder
+        eng = getattr(dec, "_hip", None)
+        if not (self.fused_mh and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.int64 and z0.device == x.device):
+            return False
+        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
+            return False
+        try:
+            eng.ensure(x.device)
+        except _lib.LvaeError:
+            return False
+        return eng.cond_ll_supported(x.size(1))
+
+    def sample_from_posterior(self, x, nsamples, chains=1, burn_in=None, thin=None, std=None, noise=None, generator=None,
+                              iters_per_launch=None, return_info=False):
+        """Random-walk Metropolis-Hastings samples from the model posterior p(z|x) (reference vae.py:218-254)
+        -> (batch, nsamples, chains, nz) float32 on x's device, computed under torch.no_grad().
+
+        Every chain starts at a draw from q(z|x) and runs burn_in + nsamples * thin iterations: next = eps * std + cur,
+        ratio = log p(next, x) - log p(cur, x) (eval_complete_ll), accepted where u < min(exp(ratio), 1); cur is kept every
+        `thin` iterations after `burn_in`.  burn_in / thin / std default to args.mh_burn_in / mh_thin / mh_std (the
+        reference reads these three fields, which none of its scripts defines).  `chains` independent chains per sentence
+        (the reference runs one): the reference returns (batch, nsamples, 1, nz) -- its docstring says (batch, nsamples, nz),
+        but cur is (batch, 1, nz) when it is unsqueezed and concatenated -- and that singleton is the chain axis here.
+        The starting point is self.encoder.sample(x, chains)[0]; the reference looks `sample_from_inference` up on the
+        encoder, which has no such method (it is VAE's), and evidently means this.
+
+        Differences from the reference, on purpose: cur and cur_ll are SELECTED, never blended (mask * next + (1 - mask) * cur
+        turns cur_ll into NaN for good once a proposal scores NaN; here such a proposal is rejected and the chain goes on).
+
+        noise = (z0 [B][chains][nz], eps [iterations][B][chains][nz], u [iterations][B][chains]) injects every random draw
+        (parity tests).  Without it eps and u are drawn with torch.randn / torch.rand on x's device (`generator` optional),
+        one pair of draws per launch chunk of `iters_per_launch` iterations: a seed therefore reproduces a chain only for
+        the same iters_per_launch.
+
+        Routes (class switch fused_mh = False forces the second):
+          "chain": eval-mode LSTM decoder inside the fused kernel's envelope -- the whole chain on the device in launches of
+                   at most iters_per_launch iterations (default: the largest n with n * (T - 1) <= 2048), 16 chains of a
+                   sentence per workgroup; decoder.log_probability is never called;
+          "step":  everything else (H > 128, the PixelCNN decoder, a training-mode decoder with dropout, which draws its
+                   masks as the reference would): one eval_cond_ll(x, next) plus one lv_mh_step_f32 launch per iteration.
+        Neither reads anything back to the host inside the chain.
+
+        return_info: also {"accept_rate": [B, chains], "log_joint": [B, chains] (the final cur_ll), "route", "iterations",
+        "ratios": [iterations, B, chains], "accepts": [iterations, B, chains] (the per-iteration ratio and accept flag)}."""
+        a = self.args
+        vals = [burn_in, thin, std]
+        for i, f in enumerate(("mh_burn_in", "mh_thin", "mh_std")):
+            if vals[i] is None:
+                if not hasattr(a, f):
+                    raise ValueError("sample_from_posterior: pass burn_in / thin / std or set args.mh_burn_in, args.mh_thin "
+                                     "and args.mh_std (missing: %s)" % f)
+                vals[i] = getattr(a, f)
+        burn_in, thin, std = int(vals[0]), int(vals[1]), float(vals[2])
+        nsamples, chains = int(nsamples), int(chains)
+        if nsamples < 1 or chains < 1 or burn_in < 0 or thin < 1:
+            raise ValueError("sample_from_posterior: nsamples >= 1, chains >= 1, burn_in >= 0, thin >= 1 expected")
+        total = burn_in + nsamples * thin
+        with torch.no_grad():
+            dev = x.device if torch.is_tensor(x) else x[0].device
+            if noise is not None:
+                z0, eps_all, u_all = noise
+                for name, t in (("z0", z0), ("eps", eps_all), ("u", u_all)):
+                    if t.device != dev:          # the kernels take raw pointers: refused before anything is launched
+                        raise _lib.LvaeError("sample_from_posterior: %s is on %s, x on %s" % (name, t.device, dev))
+                if eps_all.shape[0] != total or u_all.shape[0] != total:
+                    raise ValueError("sample_from_posterior: noise for %d iterations expected" % total)
+            else:
+                z0 = self.encoder.sample(x, chains)[0]
+                eps_all = u_all = None
+            z0 = z0.detach().float().contiguous()
+            B, C, nz = z0.shape
+            if C != chains or nz != self.nz:
+                raise ValueError("sample_from_posterior: z0 [B][%d][%d] expected, got %s" % (chains, self.nz, tuple(z0.shape)))
+
+            def draw(i0, n):
+                if eps_all is not None:
+                    return eps_all[i0:i0 + n].float().contiguous(), u_all[i0:i0 + n].float().contiguous()
+                return (torch.randn(n, B, C, nz, device=dev, generator=generator),
+                        torch.rand(n, B, C, device=dev, generator=generator))
+
+            if self._fused_mh_ok(x, z0):
+                route = "chain"
+                r = self.decoder._hip.mh_chain(x, z0, draw, burn_in, thin, nsamples, std, iters_per_launch)
+                samples, log_joint, accepts, ratios, flags = r["samples"], r["log_joint"], r["accepts"], r["ratios"], r["flags"]
+            else:
+                route = "step"
+                samples, log_joint, accepts, ratios, flags = self._mh_by_steps(x, z0, draw, burn_in, thin, nsamples, std,
+                                                                               iters_per_launch)
+        if not return_info:
+            return samples
+        return samples, {"accept_rate": accepts.float() / float(total), "log_joint": log_joint, "route": route,
+                         "iterations": total, "ratios": ratios, "accepts": flags}
+
+    def _mh_by_steps(self, x, z0, draw, burn_in, thin, nsamples, std, iters_per_launch):
+        """Route "step" of sample_from_posterior: eval_cond_ll for the scores, lv_mh_step_f32 for everything else."""
+        dev = z0.device
+        B, C, nz = z0.shape
+        total = burn_in + nsamples * thin
+        if iters_per_launch is None:
+            T = x.size(1) if (torch.is_tensor(x) and x.dim() == 2) else 33
+            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
+        per = int(iters_per_launch)
+        if per < 1:
+            raise ValueError("sample_from_posterior: iters_per_launch >= 1 expected")
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        cur, prop = z0.clone(), z0.clone()
+        cur_ll, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **i32)
+        samples = torch.empty(B, nsamples, C, nz, **f32)
+        ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32)
+        eps, u = draw(0, min(per, total))
+        c0 = 0                                                    # first iteration of the chunk (eps, u) covers
+        _eng.mh_step(self.eval_cond_ll(x, cur), prop, cur, cur_ll, accepts, None, eps[0], std, samples, -1, init=True)
+        for it in range(total):
+            cond = self.eval_cond_ll(x, prop)
+            u_it = u[it - c0]
+            if it + 1 < total and it + 1 - c0 >= eps.shape[0]:
+                c0 = it + 1
+                eps, u = draw(c0, min(per, total - c0))
+            eps_next = eps[it + 1 - c0] if it + 1 < total else None
+            keep = (it - burn_in) // thin if (it >= burn_in and (it - burn_in) % thin == 0) else -1
+            _eng.mh_step(cond, prop, cur, cur_ll, accepts, u_it, eps_next, std, samples, keep, ratio_out=ratios[it],
+                         flag_out=flags[it])
+        return samples, cur_ll, accepts, ratios, flags
+
     def calc_infer_mean(self, x):
         return self.encoder.forward(x)[0]
 
