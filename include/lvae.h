@@ -245,6 +245,26 @@ int lv_lstm_bwd_f32(const float* dh_ext, const float* dh_last, const uint8_t* dm
                     const float* whh, const float* gates, const float* hs, const float* cs,
                     float* dG, float* dGsum, float* ws, float* dh0, float* dc0, int tanh_init,
                     int T, int B, int H, void* stream);
+/* Variable-length batches: nn.LSTM on a pack_padded_sequence (VarLSTMEncoder enc_lstm.py:97-101, VarLSTMDecoder
+ * dec_lstm.py:419-428) as the recurrences above on the PADDED time-major buffers.  steps: int32 [B] on the device, row b is
+ * active at timestep t when t < steps[b] (encoder: the sentence length; decoder: length - 1); max_steps: the host's bound on its
+ * entries, 0 <= max_steps <= T (refused otherwise; the kernels only compare t < steps[b], so no entry can reach past T).
+ * lv_lstm_fwd_len_f32 = lv_lstm_fwd_f32 where every step is active; an inactive step carries hs[t+1][b] = hs[t][b],
+ * cs[t+1][b] = cs[t][b] (hs[T] is each row's own last state: last_state of enc_lstm.py:101), writes hdrop[t][b] = 0 (the zero
+ * rows of pad_packed_sequence, dec_lstm.py:428) and leaves its gate record unspecified.
+ * lv_lstm_bwd_len_f32 = lv_lstm_bwd_f32 where every step is active; at an inactive step dG[t][b] = 0 exactly and dh_ext[t][b],
+ * the gate record and cs[t+1][b] are not read; dh_last enters row b at its own last step t = steps[b] - 1.  A row with
+ * steps[b] <= 0 gets dG = dGsum = dh0 = dc0 = 0.  Same scratch as the equal-length entries (lv_lstm_ws_floats). */
+int lv_lstm_fwd_len_f32(const float* gx, const float* whh, float* hs, float* cs, float* gates,
+                        const uint8_t* dmask, float dscale, float* hdrop, float* ws,
+                        const int* steps, int max_steps, int T, int B, int H, void* stream);
+int lv_lstm_bwd_len_f32(const float* dh_ext, const float* dh_last, const uint8_t* dmask, float dscale,
+                        const float* whh, const float* gates, const float* hs, const float* cs,
+                        float* dG, float* dGsum, float* ws, float* dh0, float* dc0, int tanh_init,
+                        const int* steps, int max_steps, int T, int B, int H, void* stream);
+/* token NLL [T][B] of such a batch: entries with t >= steps[b] set to zero in front of lv_vae_loss_f32 -- the weight-0 <pad>
+ * targets of VarLSTMDecoder's loss (dec_lstm.py:376-378, 471-476) */
+int lv_nll_mask_len_f32(float* nll, const int* steps, int max_steps, int T, int B, void* stream);
 
 /* ---- embeddings: nn.Embedding forward (enc_lstm.py:58, dec_lstm.py:80) fused with dropout_in (dec_lstm.py:81);
  * aten::embedding_dense_backward as a deterministic sorted-segment sum (padding_idx row skipped: dec_lstm.py:28) */

@@ -210,11 +210,15 @@ struct LstmFwdP {
     const uint8_t* dmask; float dscale; float* hdrop;
     int T, B, H, Kq, MBTp;
     int gx_unit_major;     // gx rows hold (i,f,g,o) of unit u at columns 4u..4u+3 instead of g*H + u
+    const int* steps;      // LEN instantiations only: [B] active timesteps per row (row b runs while t < steps[b])
 };
 
 // ABL: ablation switches for profiles/microbench/lstm_step_probe.hip only (product launches use ABL = 0):
 //      1 = skip the recurrent matmul, 2 = skip the gate math and all stores except h, 4 = skip the epilogue operand loads
-template <int MB, int ABL = 0, bool BF = false>
+// LEN: variable-length batch (lv_lstm_fwd_len_f32).  A row with t >= steps[b] is frozen: its state of step t is carried to
+//      index t+1 (standard and packed copies), its hdrop entry is 0 and its gate record is left alone.  Active rows run the
+//      very same arithmetic as the LEN = false instantiation.
+template <int MB, int ABL = 0, bool BF = false, bool LEN = false>
 __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwdP p, int t) {
     __shared__ float red[4][MB][16][17];
     const int tid = (int)threadIdx.x, l = tid & 63, w = tid >> 6;
@@ -236,6 +240,8 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwdP p, int t) {
     // epilogue operands for this thread's (batch row, unit) pairs: issue the loads before the matmul
     constexpr int NP = (64 * MB + 255) / 256;
     float pre[NP][4], cp[NP], keep[NP];
+    float hprev[NP];                                 // LEN: the state a frozen row carries on
+    bool live[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         const int pi = tid + 256 * q;
@@ -252,6 +258,12 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwdP p, int t) {
         cp[q] = ok ? c_prev[(long)b * H + u] : 0.f;
         keep[q] = 1.f;                               // dropout keep-mask x scale of the output copy, fetched up front
         if (ok && p.hdrop && p.dmask) keep[q] = p.dmask[((long)b * p.T + t) * H + u] ? p.dscale : 0.f;
+        live[q] = true;
+        hprev[q] = 0.f;
+        if (LEN && ok) {
+            live[q] = t < p.steps[b];
+            if (!live[q]) hprev[q] = p.hs[(long)t * BH + (long)b * H + u];
+        }
     }
 
     // recurrent matmul: this workgroup's 16 gate columns, K split over the 4 waves in units of 16
@@ -291,6 +303,13 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwdP p, int t) {
                 a[g] = pre[q][g] + s;
             }
             if (ABL & 2) { h_out[(long)b * H + u] = a[0] + a[1] + a[2] + a[3]; continue; }
+            if (LEN && !live[q]) {
+                c_out[(long)b * H + u] = cp[q];
+                h_out[(long)b * H + u] = hprev[q];
+                hp_out[((long)nb * p.MBTp + (b >> 4)) * 64 + (b & 15) * 4 + uu] = hprev[q];
+                if (p.hdrop) p.hdrop[(long)t * BH + (long)b * H + u] = 0.f;
+                continue;
+            }
             float ig, fg, gg, og, h;
             float c;
             if (BF) {
@@ -324,18 +343,35 @@ struct LstmBwdP {
     float* dG; float* dGsum; float* dGp; float* dh_part; float* dc_rec;
     int T, B, H, KS, Kq4, MBTp;
     uint16_t* dG16;        // optional bf16 image of dG for lv_gemm_b16 (bf16 path; dG may then be null)
+    const int* steps;      // LEN instantiations only: [B] active timesteps per row
 };
 
 // elementwise part of BPTT step t (KS = number of split-K slabs of the previous step's matmul, compile-time so
 // that all slab loads are issued together)
-template <int KS, bool BF = false>
+// LEN: variable-length batch (lv_lstm_bwd_len_f32).  Row b's chain starts at its own last step t = steps[b] - 1 (that is
+//      where dh_last enters and where nothing is read from the slabs, dc_rec or dGsum); at t >= steps[b] the row writes
+//      dG = 0 (standard and packed, so the recurrent product hands on an exact zero) and reads nothing else.
+template <int KS, bool BF = false, bool LEN = false>
 __global__ __launch_bounds__(256) void lstm_step_bwd_elem_kernel(LstmBwdP p, int t) {
     const int B = p.B, H = p.H;
     const long BH = (long)B * H;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= BH) return;
     const int b = (int)(idx / H), u = (int)(idx % H);
-    const bool first = (t == p.T - 1);
+    const int nsteps = LEN ? p.steps[b] : p.T;
+    if (LEN && t >= nsteps) {
+        const long gi0 = (long)t * B * 4 * H + (long)b * 4 * H + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = g * H + u;
+            if (p.dG) p.dG[gi0 + (long)g * H] = 0.f;
+            p.dGp[((long)(n >> 2) * p.MBTp + (b >> 4)) * 64 + (b & 15) * 4 + (n & 3)] = 0.f;
+            if (t == 0) p.dGsum[(long)b * 4 * H + u + (long)g * H] = 0.f;      // a row with no active step at all
+        }
+        if (t == 0) p.dc_rec[idx] = 0.f;
+        return;
+    }
+    const bool first = (t == nsteps - 1);
     float dh = 0.f;
     if (p.dh_ext) {
         float m = 1.f;
@@ -495,10 +531,10 @@ inline Geo geo(int B, int H, bool bf = false) {
     return g;
 }
 
-template <int MB, bool BF>
+template <int MB, bool BF, bool LEN = false>
 int launch_fwd_steps(const LstmFwdP& p, void* stream) {
     dim3 grid((unsigned)lv_cdiv(p.H, 4), (unsigned)(p.MBTp / MB)), block(256);
-    for (int t = 0; t < p.T; ++t) LV_LAUNCH((lstm_step_fwd_kernel<MB, 0, BF>), grid, block, 0, stream, p, t);
+    for (int t = 0; t < p.T; ++t) LV_LAUNCH((lstm_step_fwd_kernel<MB, 0, BF, LEN>), grid, block, 0, stream, p, t);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }
@@ -509,21 +545,25 @@ void launch_bwd_mm(const LstmBwdP& p, int t, void* stream) {
     LV_LAUNCH((lstm_step_bwd_mm_kernel<MB, BF>), grid, block, 0, stream, p, t);
 }
 
-template <bool BF>
+template <bool BF, bool LEN = false>
 void launch_bwd_elem(const LstmBwdP& p, int t, dim3 egrid, void* stream) {
     dim3 block(256);
     switch (p.KS) {
-        case 1: LV_LAUNCH((lstm_step_bwd_elem_kernel<1, BF>), egrid, block, 0, stream, p, t); break;
-        case 2: LV_LAUNCH((lstm_step_bwd_elem_kernel<2, BF>), egrid, block, 0, stream, p, t); break;
-        case 4: LV_LAUNCH((lstm_step_bwd_elem_kernel<4, BF>), egrid, block, 0, stream, p, t); break;
-        default: LV_LAUNCH((lstm_step_bwd_elem_kernel<8, BF>), egrid, block, 0, stream, p, t); break;
+        case 1: LV_LAUNCH((lstm_step_bwd_elem_kernel<1, BF, LEN>), egrid, block, 0, stream, p, t); break;
+        case 2: LV_LAUNCH((lstm_step_bwd_elem_kernel<2, BF, LEN>), egrid, block, 0, stream, p, t); break;
+        case 4: LV_LAUNCH((lstm_step_bwd_elem_kernel<4, BF, LEN>), egrid, block, 0, stream, p, t); break;
+        default: LV_LAUNCH((lstm_step_bwd_elem_kernel<8, BF, LEN>), egrid, block, 0, stream, p, t); break;
     }
 }
 
-template <bool BF>
+// LEN: steps [B] on the device, max_steps = the host's bound on its entries (checked against T; the kernels compare
+// t < steps[b] only, so a larger entry cannot reach past T)
+template <bool BF, bool LEN = false>
 int lstm_fwd_impl(const float* gx, const float* whh, float* hs, float* cs, float* gates,
                   const uint8_t* dmask, float dscale, float* hdrop, float* ws, int T, int B, int H, void* stream,
-                  int gx_unit_major = 0) {
+                  int gx_unit_major = 0, const int* steps = nullptr, int max_steps = 0) {
+    if (LEN && !steps) return LV_ERR_ARG;
+    if (LEN && (max_steps < 0 || max_steps > T)) return LV_ERR_SHAPE;
     if (!gx || !whh || !hs || !cs || !gates || !ws) return LV_ERR_ARG;
     if (T < 0 || B <= 0 || H <= 0) return LV_ERR_SHAPE;
     if (dmask && !hdrop) return LV_ERR_ARG;
@@ -544,20 +584,22 @@ int lstm_fwd_impl(const float* gx, const float* whh, float* hs, float* cs, float
         LV_LAUNCH(pack_w_fwd_kernel, dim3((unsigned)lv_cdiv((long)g.NBf * g.Kq * 16, 256)), dim3(256), 0, stream, whh, wp, H, g.Kq);
         LV_LAUNCH(pack_act_kernel, dim3((unsigned)lv_cdiv((long)B * H, 256)), dim3(256), 0, stream, (const float*)hs, hp, B, H, g.MBTp);
     }
-    LstmFwdP p{gx, wp, hs, cs, gates, hp, dmask, dscale, hdrop, T, B, H, g.Kq, g.MBTp, gx_unit_major};
+    LstmFwdP p{gx, wp, hs, cs, gates, hp, dmask, dscale, hdrop, T, B, H, g.Kq, g.MBTp, gx_unit_major, steps};
     switch (g.MB) {
-        case 1: return launch_fwd_steps<1, BF>(p, stream);
-        case 2: return launch_fwd_steps<2, BF>(p, stream);
-        case 4: return launch_fwd_steps<4, BF>(p, stream);
-        default: return launch_fwd_steps<8, BF>(p, stream);
+        case 1: return launch_fwd_steps<1, BF, LEN>(p, stream);
+        case 2: return launch_fwd_steps<2, BF, LEN>(p, stream);
+        case 4: return launch_fwd_steps<4, BF, LEN>(p, stream);
+        default: return launch_fwd_steps<8, BF, LEN>(p, stream);
     }
 }
 
-template <bool BF>
+template <bool BF, bool LEN = false>
 int lstm_bwd_impl(const float* dh_ext, const float* dh_last, const uint8_t* dmask, float dscale,
                   const float* whh, const float* gates, const float* hs, const float* cs,
                   float* dG, float* dGsum, float* ws, float* dh0, float* dc0, int tanh_init,
-                  int T, int B, int H, void* stream, uint16_t* dG16 = nullptr) {
+                  int T, int B, int H, void* stream, uint16_t* dG16 = nullptr, const int* steps = nullptr, int max_steps = 0) {
+    if (LEN && !steps) return LV_ERR_ARG;
+    if (LEN && (max_steps < 0 || max_steps > T)) return LV_ERR_SHAPE;
     if (!whh || !gates || !cs || (!dG && !dG16) || !dGsum || !ws) return LV_ERR_ARG;
     if (T <= 0 || B <= 0 || H <= 0) return LV_ERR_SHAPE;
     if (tanh_init && !hs) return LV_ERR_ARG;
@@ -573,12 +615,12 @@ int lstm_bwd_impl(const float* dh_ext, const float* dh_last, const uint8_t* dmas
     else
         LV_LAUNCH(pack_w_bwd_kernel, dim3((unsigned)lv_cdiv((long)g.NBb * g.Kq4 * 16, 256)), dim3(256), 0, stream, whh, wpT, H, g.Kq4);
     if (g.MBTp * 16 != B || g.Kq4 * (BF ? 8 : 4) != 4 * H) hipMemsetAsync(dGp, 0, (size_t)g.dGp * sizeof(float), (hipStream_t)stream);
-    LstmBwdP p{dh_ext, dh_last, dmask, dscale, wpT, gates, cs, dG, dGsum, dGp, part, dcrec, T, B, H, g.KS, g.Kq4, g.MBTp, dG16};
+    LstmBwdP p{dh_ext, dh_last, dmask, dscale, wpT, gates, cs, dG, dGsum, dGp, part, dcrec, T, B, H, g.KS, g.Kq4, g.MBTp, dG16, steps};
     const long BH = (long)B * H;
     const bool need_h0 = (dh0 != nullptr) || tanh_init;
     dim3 egrid((unsigned)lv_cdiv(BH, 256)), block(256);
     for (int t = T - 1; t >= 0; --t) {
-        launch_bwd_elem<BF>(p, t, egrid, stream);
+        launch_bwd_elem<BF, LEN>(p, t, egrid, stream);
         if (t > 0 || need_h0) {
             switch (g.MB) {
                 case 1: launch_bwd_mm<1, BF>(p, t, stream); break;
@@ -688,6 +730,50 @@ extern "C" int lv_lstm_fwd_f32_ug(const float* gx, const float* whh, float* hs, 
                                   const uint8_t* dmask, float dscale, float* hdrop, float* ws,
                                   int T, int B, int H, void* stream) {
     return lstm_fwd_impl<false>(gx, whh, hs, cs, gates, dmask, dscale, hdrop, ws, T, B, H, stream, 1);
+}
+
+// ---- variable-length batches (reference VarLSTMEncoder enc_lstm.py:77-126, VarLSTMDecoder dec_lstm.py:370-476: nn.LSTM on a
+// packed sequence) -------------------------------------------------------------------------------------------------------------
+// lv_lstm_fwd_f32 / lv_lstm_bwd_f32 with steps [B] (int32, device): row b is active at timestep t when t < steps[b].
+//   forward: an inactive step carries hs / cs (and the packed copy of h) on, so hs[T] is every row's own last state; hdrop = 0
+//            there; the gate record of an inactive step is unspecified.
+//   BPTT:    dG = 0 exactly at an inactive step; dh_last enters row b at t = steps[b] - 1; dh_ext, the gate record and
+//            cs[t+1] of an inactive step are not read.  A row with steps[b] <= 0 gets dG = dGsum = dc0 = dh0 = 0.
+// max_steps: the host's bound on the entries of steps, 0 <= max_steps <= T (anything else is refused before a launch).
+extern "C" int lv_lstm_fwd_len_f32(const float* gx, const float* whh, float* hs, float* cs, float* gates,
+                                   const uint8_t* dmask, float dscale, float* hdrop, float* ws,
+                                   const int* steps, int max_steps, int T, int B, int H, void* stream) {
+    return lstm_fwd_impl<false, true>(gx, whh, hs, cs, gates, dmask, dscale, hdrop, ws, T, B, H, stream, 0, steps, max_steps);
+}
+
+extern "C" int lv_lstm_bwd_len_f32(const float* dh_ext, const float* dh_last, const uint8_t* dmask, float dscale,
+                                   const float* whh, const float* gates, const float* hs, const float* cs,
+                                   float* dG, float* dGsum, float* ws, float* dh0, float* dc0, int tanh_init,
+                                   const int* steps, int max_steps, int T, int B, int H, void* stream) {
+    return lstm_bwd_impl<false, true>(dh_ext, dh_last, dmask, dscale, whh, gates, hs, cs, dG, dGsum, ws, dh0, dc0, tanh_init,
+                                      T, B, H, stream, nullptr, steps, max_steps);
+}
+
+namespace {
+// token NLL [T][B] of a variable-length batch: entries at t >= steps[b] set to zero
+__global__ __launch_bounds__(256) void nll_mask_len_kernel(float* __restrict__ nll, const int* __restrict__ steps, long n, int B) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int t = (int)(idx / B), b = (int)(idx % B);
+    if (t >= steps[b]) nll[idx] = 0.f;
+}
+}  // namespace
+
+// nll [T][B] (lv_softmax_nll_fwd_f32's output): zero where t >= steps[b], in front of lv_vae_loss_f32's sum over t -- the
+// weight-0 <pad> targets of the reference's loss (dec_lstm.py:384-386, 467-470)
+extern "C" int lv_nll_mask_len_f32(float* nll, const int* steps, int max_steps, int T, int B, void* stream) {
+    if (!nll || !steps) return LV_ERR_ARG;
+    if (T < 0 || B <= 0 || max_steps < 0 || max_steps > T) return LV_ERR_SHAPE;
+    if (T == 0) return LV_OK;
+    const long n = (long)T * B;
+    LV_LAUNCH(nll_mask_len_kernel, dim3((unsigned)lv_cdiv(n, 256)), dim3(256), 0, stream, nll, steps, n, B);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
 }
 
 namespace {

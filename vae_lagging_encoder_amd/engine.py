@@ -578,12 +578,134 @@ def _xch_flags(wi, kind, rows, device, T=1):
     return fl
 
 
-def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, device):
+class SeqLengths(object):
+    """The validated sentence lengths of a variable-length batch (x [B][T], lengths) -- reference VarLSTMEncoder / VarLSTMDecoder,
+    enc_lstm.py:95-99, dec_lstm.py:391-420.  A length counts every token of its row, <s> and </s> included.  `lengths`: a list of
+    ints or an integer tensor on any device, one per row, 2 <= length <= T, in any order (the reference wants them sorted and
+    max(length) == T; neither is needed here).  Anything else raises ValueError before a launch.
+    .host: the lengths as ints; .max; .enc: int32 [B] on `device` (the encoder's step counts); .dec(ns): int32 [B*ns], length - 1
+    repeated over a sentence's samples (the decoder predicts no <s>)."""
+
+    def __init__(self, lengths, B, T, device):
+        if torch.is_tensor(lengths):
+            if lengths.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) or lengths.dim() != 1:
+                raise ValueError("sentence lengths: a 1-D integer tensor or a list of ints expected, got %s %s"
+                                 % (lengths.dtype, tuple(lengths.shape)))
+            host = [int(v) for v in lengths.detach().cpu().tolist()]
+        else:
+            try:
+                host = list(lengths)
+            except TypeError:
+                raise ValueError("sentence lengths: a 1-D integer tensor or a list of ints expected, got %r" % (type(lengths),))
+            if not all(isinstance(v, int) and not isinstance(v, bool) for v in host):
+                raise ValueError("sentence lengths: a list of ints expected")
+        if len(host) != B:
+            raise ValueError("sentence lengths: %d values for a batch of %d sentences" % (len(host), B))
+        if B > 0 and min(host) < 2:
+            raise ValueError("sentence lengths: every sentence holds at least <s> and </s>; got a length of %d" % min(host))
+        if B > 0 and max(host) > T:
+            raise ValueError("sentence lengths: a length of %d in a batch tensor of %d columns" % (max(host), T))
+        self.host, self.B, self.T = host, B, T
+        self.device = torch.device(device)
+        self.max = max(host) if host else 0
+        self.enc = torch.tensor(host, dtype=torch.int32).to(self.device)
+        self._dec = {}
+
+    def dec(self, ns=1):
+        d = self._dec.get(ns)
+        if d is None:
+            d = self._dec[ns] = (self.enc - 1).repeat_interleave(ns).contiguous()
+        return d
+
+    @staticmethod
+    def of(lengths, B, T, device):
+        if isinstance(lengths, SeqLengths) and (lengths.B, lengths.T, lengths.device) == (B, T, torch.device(device)):
+            return lengths
+        return SeqLengths(lengths.host if isinstance(lengths, SeqLengths) else lengths, B, T, device)
+
+
+def varlen_batch(x):
+    """(x [B][T], lengths) -> (x cut to max(lengths) columns, SeqLengths): the validated form of a variable-length batch.  The
+    columns beyond the longest sentence are padding that no row ever reaches.  Idempotent."""
+    xt, lengths = x
+    if not (torch.is_tensor(xt) and xt.dim() == 2 and xt.dtype == torch.int64):
+        raise ValueError("a variable-length batch is a pair (int64 tensor [batch][seq_len], lengths)")
+    B, T = xt.shape
+    L = SeqLengths.of(lengths, B, T, xt.device)
+    if B > 0 and L.max < T:
+        xt = xt[:, :L.max].contiguous()
+        L = SeqLengths.of(L, B, L.max, xt.device)
+    return xt, L
+
+
+def length_groups(L):
+    """[(length, int64 row indices on the device)] of the by-length route, in decreasing length."""
+    by = {}
+    for b, n in enumerate(L.host):
+        by.setdefault(n, []).append(b)
+    return [(n, torch.tensor(by[n], dtype=torch.int64).to(L.device)) for n in sorted(by, reverse=True)]
+
+
+class GroupedBackward(object):
+    """The by-length route's book-keeping (VarLSTMEncoder / VarLSTMDecoder with masked = False): an engine keeps one step in
+    flight and its backward writes the flat gradient buffer with '=' semantics, so a batch cut into equal-length groups runs one
+    forward per group -- each on the workspace of its own (rows, T) shape -- with the engine's record of the step (`last` and
+    friends) set aside, and one backward per group with that record put back, the groups' gradients summed by lv_add_f32."""
+    FIELDS = ("last", "last_ns", "last_steps", "_sort")
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.saved = []
+
+    def after_forward(self, w):
+        self.saved.append(({k: getattr(self.eng, k, None) for k in self.FIELDS}, w))
+
+    def backward(self, i, current_ws, run):
+        """Group i: restore its record, check that its workspace is still the one its forward wrote, run(gen), add up."""
+        eng = self.eng
+        rec, w = self.saved[i]
+        for k, val in rec.items():
+            setattr(eng, k, val)
+        if current_ws() is not w:
+            raise _lib.LvaeError("the by-length route's activations were dropped from the workspace cache between forward and backward "
+                                 "(raise engine.WORKSPACE_BUDGET_FRACTION)")
+        out = run(rec["last"][-1])
+        if hasattr(eng, "join"):
+            eng.join()
+        f = eng.flat
+        lib, s = eng.lib, stream_ptr(f.device)
+        if i == 0:
+            self.total = f.grad.clone()
+        else:
+            lib.lv_add_f32(P(self.total), P(f.grad), P(self.total), f.grad.numel(), s)
+        if i == len(self.saved) - 1 and i > 0:
+            f.grad.copy_(self.total)
+        return out
+
+
+def _refuse_bf16_lengths(eng):
+    if eng.precision == "bf16":
+        raise _lib.LvaeError("variable-length batches (x, lengths) run the exact-f32 configuration only: the bf16 and the persistent "
+                             "recurrences have no length-aware form; call set_precision('f32') or batch by length")
+
+
+def _same_device(what, dev, **operands):
+    """The kernels take raw pointers: an operand on another device is refused before anything is launched."""
+    for name, t in operands.items():
+        if t is not None and t.device != dev:
+            raise _lib.LvaeError("%s: %s is on %s, x on %s" % (what, name, t.device, dev))
+
+
+def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, device, steps=None):
     """The forward recurrence of one LSTM layer: exact f32, bf16 launch-per-step, or (bf16 image path on a >= 256-CU
-    device, H = 1024, B <= 128) the single persistent launch of lv_lstm_persist16.hip."""
+    device, H = 1024, B <= 128) the single persistent launch of lv_lstm_persist16.hip.  steps = (int32 [B] on the device,
+    their maximum): the length-aware exact-f32 recurrence (lv_lstm_fwd_len_f32), row b active while t < steps[b]."""
     args = (Gx, whh, P(w.hs), P(w.cs), P(w.gates), mask, scale, hdrop)
     w.saved_layout = ("canonical", T, B, 0)
-    if eng.precision != "bf16":
+    if steps is not None:
+        _refuse_bf16_lengths(eng)
+        lib.lv_lstm_fwd_len_f32(*args, P(w.lstm_ws), P(steps[0]), steps[1], T, B, H, s)
+    elif eng.precision != "bf16":
         lib.lv_lstm_fwd_f32(*args, P(w.lstm_ws), T, B, H, s)
     elif img is None:
         lib.lv_lstm_fwd_bf16(*args, P(w.lstm_ws), T, B, H, s)
@@ -625,8 +747,14 @@ def _need_canonical_saved(w):
                              "backward" % (lay,))
 
 
-def _lstm_backward(eng, lib, s, img, w, dh_ext, dh_last, mask, scale, whh, dh0, dc0, tanh_init, T, B, H, device):
-    """BPTT of one LSTM layer: exact f32, bf16 two launches per step, or the single persistent launch where supported."""
+def _lstm_backward(eng, lib, s, img, w, dh_ext, dh_last, mask, scale, whh, dh0, dc0, tanh_init, T, B, H, device, steps=None):
+    """BPTT of one LSTM layer: exact f32, bf16 two launches per step, or the single persistent launch where supported.
+    steps: as _lstm_forward's (lv_lstm_bwd_len_f32)."""
+    if steps is not None:
+        _refuse_bf16_lengths(eng)
+        lib.lv_lstm_bwd_len_f32(dh_ext, dh_last, mask, scale, whh, P(w.gates), P(w.hs), P(w.cs), P(w.dG), P(w.dGsum), P(w.lstm_ws),
+                                dh0, dc0, tanh_init, P(steps[0]), steps[1], T, B, H, s)
+        return
     if eng.precision != "bf16":
         lib.lv_lstm_bwd_f32(dh_ext, dh_last, mask, scale, whh, P(w.gates), P(w.hs), P(w.cs), P(w.dG), P(w.dGsum), P(w.lstm_ws),
                             dh0, dc0, tanh_init, T, B, H, s)
@@ -962,8 +1090,12 @@ class LSTMEncoderEngine(object):
             return w
         return c.get((B, T), build)
 
-    def forward(self, x, head=None, x_key=None):
+    def forward(self, x, head=None, x_key=None, lengths=None):
         """x int64 [B][T] on device -> mulv [B][2nz] (mu | logvar).  Keeps activations for backward().
+
+        lengths (SeqLengths, a list of ints or an integer tensor): x is a padded batch and row b holds lengths[b]
+        tokens -- mu / logvar come from the state after exactly those (enc_lstm.py:95-105).  Exact-f32 configuration only.  The
+        input projection runs over the padded positions as it is; the recurrence (lv_lstm_fwd_len_f32) freezes a finished row.
 
         head = (eps [B][ns][nz], z, kl): also reparameterise and compute the KL in the head's launch (fused driver).
         x_key: the batch tensor x was copied from (fused driver: x is its per-shape static buffer), whose identity keys the
@@ -971,6 +1103,13 @@ class LSTMEncoderEngine(object):
         assert x.dtype == torch.int64 and x.dim() == 2
         x = x.contiguous()
         B, T = x.shape
+        steps = None
+        if lengths is not None:
+            _refuse_bf16_lengths(self)
+            if head is not None:
+                raise _lib.LvaeError("the fused head takes equal-length batches only")
+            lengths = SeqLengths.of(lengths, B, T, x.device)
+            steps = (lengths.enc, lengths.max)
         f = self.ensure(x.device)
         lib, s = self.lib, stream_ptr(x.device)
         V, ni, H, nz2 = self.dims()
@@ -1019,7 +1158,7 @@ class LSTMEncoderEngine(object):
             self._exact_recurrence(lib, s, img, w, gx_unit_major, T, B, H, x.device)
         else:
             with _prof("lstm_fwd_enc", float(T), 1 if _persistent_ok(self, img, B, H, x.device, _PERSIST_MAX_B) else T):
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, T, B, H, x.device)
+                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, T, B, H, x.device, steps=steps)
         if head is not None and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
             eps, z, kl = head
             _gemm(lib, s, 0, 1, B, nz2, H, P(w.hs, T * B * H), H, P(v["linear.weight"]), H, P(w.mulv), nz2)
@@ -1032,6 +1171,7 @@ class LSTMEncoderEngine(object):
             _gemm(lib, s, 0, 1, B, nz2, H, P(w.hs, T * B * H), H, P(v["linear.weight"]), H, P(w.mulv), nz2)
         self.gen += 1
         self.last = (x, B, T, self.gen)
+        self.last_steps = steps
         return w.mulv
 
     def _exact_forward_split(self, lib, s, img, w, x, T, B, V, ni, H):
@@ -1138,7 +1278,8 @@ class LSTMEncoderEngine(object):
             _gemm(lib, s, 1, 0, nz2, H, B, P(dmulv), nz2, P(w.hs, T * B * H), H, P(gv["linear.weight"]), H)
         img = self._b16(B, T)
         with _prof("lstm_bwd_enc", float(T), 1 if _persistent_ok(self, img, B, H, x.device, _PERSIST_BWD_MAX_B) else 2 * T):
-            _lstm_backward(self, lib, s, img, w, None, P(w.dhT), None, 1.0, P(v["lstm.weight_hh_l0"]), None, None, 0, T, B, H, x.device)
+            _lstm_backward(self, lib, s, img, w, None, P(w.dhT), None, 1.0, P(v["lstm.weight_hh_l0"]), None, None, 0, T, B, H, x.device,
+                           steps=getattr(self, "last_steps", None))
         if after_bptt is not None:
             after_bptt()
         def embed_grad():
@@ -1378,8 +1519,14 @@ class LSTMDecoderEngine(object):
             return self.wsc.get(("b16lstm", Bd // ns, ns, Td), lambda: _LstmImagesMS(self.wsc, Td, Bd // ns, ns, ni, H))
         return self.wsc.get(("b16lstm", Bd, Td), lambda: _LstmImages(self.wsc, Td * Bd, ni, H, key=("b16lstm", Bd, Td)))
 
-    def forward(self, x, z, mask_in, mask_out, p_in, p_out, want_rec=True, x_key=None):
-        """x int64 [B][T]; z [B][ns][nz]; masks uint8 keep-masks in the reference's batch-first layout or None (eval mode):
+    def forward(self, x, z, mask_in, mask_out, p_in, p_out, want_rec=True, x_key=None, lengths=None):
+        """lengths (SeqLengths, a list of ints or an integer tensor): x is a padded batch, row b holds lengths[b]
+        tokens and decoder row b * ns + s runs lengths[b] - 1 steps (dec_lstm.py:391-435); rec sums the token NLL over those steps
+        only.  Exact-f32 configuration only.  The recurrence (lv_lstm_fwd_len_f32) leaves zero rows in the projection's input at
+        the padded positions and the BPTT (lv_lstm_bwd_len_f32) ignores what the projection's backward hands it there, so the
+        vocabulary projection, the softmax and the input-side products run over the padded positions unchanged.
+
+        x int64 [B][T]; z [B][ns][nz]; masks uint8 keep-masks in the reference's batch-first layout or None (eval mode):
         mask_in [B][T-1][ni] -- one per SENTENCE, dropout_in acts before the expansion over the samples (dec_lstm.py:81-89) --,
         mask_out [B*ns][T-1][H], one per decoder row bd = b * ns + s.  Returns rec per decoder row [B*ns] (ns = 1: rec [B]; the mean
         over a sentence's rows is dec_lstm.py:146-148's value).  x_key: see LSTMEncoderEngine.forward.
@@ -1396,6 +1543,12 @@ class LSTMDecoderEngine(object):
             raise _lib.LvaeError("the HIP decoder path takes z of shape [B, nsamples, nz]; got %s for a batch of %d" % (tuple(z.shape), B))
         ns = int(z.shape[1])
         Bd = B * ns
+        steps = None
+        if lengths is not None:
+            _refuse_bf16_lengths(self)
+            _same_device("the length-aware decoder", x.device, z=z, mask_in=mask_in, mask_out=mask_out)
+            lengths = SeqLengths.of(lengths, B, T, x.device)
+            steps = (lengths.dec(ns), lengths.max - 1)
         z2 = z.reshape(Bd, -1).contiguous()
         f = self.ensure(x.device)
         lib, s = self.lib, stream_ptr(x.device)
@@ -1457,7 +1610,8 @@ class LSTMDecoderEngine(object):
             if late_mask:
                 _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, Bd, H, x.device)
             else:
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device)
+                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device,
+                              steps=steps)
         hs3 = HS3_CVT and late_mask and img is not None
         if hs3:
             # O, O^T (dropout_out applied) and the BPTT-side h_prev^T from ONE read of hs: backward() skips its own conversion
@@ -1484,6 +1638,8 @@ class LSTMDecoderEngine(object):
             _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
         if not (b16 is not None and self.fused_nll):
             lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
+        if steps is not None:
+            lib.lv_nll_mask_len_f32(P(w.nll), P(steps[0]), steps[1], Td, Bd, s)      # the weight-0 <pad> targets (dec_lstm.py:376-378)
         if want_rec:
             # rec[bd] = sum_t nll[t][bd]  (loss assembly kernel with kl weight 0); the fused driver sums nll itself
             lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
@@ -1492,6 +1648,7 @@ class LSTMDecoderEngine(object):
             img.hT_gen = self.gen if hs3 else None
         self.last = (x, z2, mask_in, mask_out, sc_in, sc_out, B, T, self.gen)
         self.last_ns = ns
+        self.last_steps = steps
         return w.rec
 
     def cond_ll_supported(self, T):
@@ -1612,6 +1769,10 @@ class LSTMDecoderEngine(object):
         wih = v["lstm.weight_ih_l0"]
         gwih = gv["lstm.weight_ih_l0"]
         dev = x.device
+        # the embedding's padding row gets no gradient: V - 1 for LSTMDecoder (padding_idx = -1), vocab['<pad>'] for
+        # VarLSTMDecoder (dec_lstm.py:375)
+        pad_idx = self.m.embed.padding_idx
+        pad_idx = V - 1 if pad_idx is None else int(pad_idx)
         b16 = self._b16(Bd, Td, ns)
         if b16 is not None and self.fused_nll:
             lib.lv_softmax_nll_bwd_h16(P(b16.l16), b16.ldv, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
@@ -1652,7 +1813,7 @@ class LSTMDecoderEngine(object):
                 lib.lv_keep_scale_f32(P(w.dO), P(mask_out), sc_out, Td, Bd, H, s)      # dropout_out backward, once, loads along H
         with _prof("lstm_bwd_dec", float(Td), 1 if late_mask else 2 * Td):
             _lstm_backward(self, lib, s, img, w, P(w.dO), None, None if late_mask else P(mask_out), 1.0 if late_mask else sc_out,
-                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, Bd, H, dev)
+                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, Bd, H, dev, steps=getattr(self, "last_steps", None))
         ctx, sws = self._fork(dev)                    # side: everything that only needs dG (runs under the encoder's backward)
         with ctx:
             s2 = stream_ptr(dev)
@@ -1672,10 +1833,10 @@ class LSTMDecoderEngine(object):
             if self.fold and "embed" in self.fold:
                 sq, only = self.fold["embed"]
                 lib.lv_embed_scatter_full_sumsq_f32(P(w.dX), P(mask_in), sc_in, P(self._sort[0]), P(self._sort[1]), Td, B,
-                                                    P(gv["embed.weight"]), ni, V, V - 1, P(sq), int(only), s2)
+                                                    P(gv["embed.weight"]), ni, V, pad_idx, P(sq), int(only), s2)
             else:
                 lib.lv_embed_scatter_full_f32(P(w.dX), P(mask_in), sc_in, P(self._sort[0]), P(self._sort[1]), Td, B, P(gv["embed.weight"]), ni,
-                                              V, V - 1, s2)
+                                              V, pad_idx, s2)
         self._mark_pending(dev)
         if not fused_ends_ok(Bd, nz):
             _gemm(lib, s, 1, 0, 4 * H, nz, Bd, P(w.dGsum), 4 * H, P(z2), nz, P(gwih, ni), ni + nz)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ... import _lib
 from ... import engine as _eng
 from .decoder import DecoderBase
 
@@ -33,6 +34,61 @@ class _DecoderFn(torch.autograd.Function):
         dz = eng.backward(drec, ctx.gen).clone().view(ctx.zshape)
         eng.join()
         return (None, None, dz, None, None, None, None) + eng.flat.deliver_grads()
+
+
+class _VarDecoderFn(torch.autograd.Function):
+    """_DecoderFn on a padded batch with lengths (engine.LSTMDecoderEngine.forward(lengths=))."""
+
+    @staticmethod
+    def forward(ctx, eng, x, z, mask_in, mask_out, p_in, p_out, lengths, *params):
+        rec = eng.forward(x, z, mask_in, mask_out, p_in, p_out, lengths=lengths)
+        ctx.eng = eng
+        ctx.gen = eng.gen
+        ctx.zshape = z.shape
+        return rec.clone()
+
+    @staticmethod
+    def backward(ctx, drec):
+        eng = ctx.eng
+        eng.flat.before_autograd_backward()
+        dz = eng.backward(drec, ctx.gen).clone().view(ctx.zshape)
+        eng.join()
+        return (None, None, dz, None, None, None, None, None) + eng.flat.deliver_grads()
+
+
+class _DecoderByLengthFn(torch.autograd.Function):
+    """The A/B route (VarLSTMDecoder.masked = False): every group of equal length through the equal-length engine, with the
+    group's slices of z and of the two keep-masks."""
+
+    @staticmethod
+    def forward(ctx, eng, x, z, mask_in, mask_out, p_in, p_out, lengths, *params):
+        B, T = x.shape
+        ns, nz = int(z.shape[1]), int(z.shape[2])
+        H = eng.dims()[2]
+        rec = torch.empty(B, ns, dtype=torch.float32, device=x.device)
+        ctx.groups = _eng.length_groups(lengths)
+        ctx.book = _eng.GroupedBackward(eng)
+        for n, rows in ctx.groups:
+            Bg = int(rows.numel())
+            m_in = None if mask_in is None else mask_in[rows, :n - 1].contiguous()
+            m_out = None if mask_out is None else mask_out.view(B, ns, T - 1, H)[rows, :, :n - 1].reshape(Bg * ns, n - 1, H).contiguous()
+            rec[rows] = eng.forward(x[rows, :n].contiguous(), z[rows].contiguous(), m_in, m_out, p_in, p_out).view(Bg, ns)
+            ctx.book.after_forward(eng._ws(Bg * ns, n - 1, ns))
+        ctx.eng, ctx.zshape = eng, (B, ns, nz)
+        return rec.view(B * ns)
+
+    @staticmethod
+    def backward(ctx, drec):
+        eng = ctx.eng
+        B, ns, nz = ctx.zshape
+        eng.flat.before_autograd_backward()
+        dz = torch.empty(B, ns, nz, dtype=torch.float32, device=drec.device)
+        drec = drec.reshape(B, ns)
+        for i, (n, rows) in enumerate(ctx.groups):
+            Bg = int(rows.numel())
+            d = drec[rows].reshape(-1).contiguous()
+            dz[rows] = ctx.book.backward(i, lambda: eng._ws(Bg * ns, n - 1, ns), lambda gen: eng.backward(d, gen)).view(Bg, ns, nz)
+        return (None, None, dz, None, None, None, None, None) + eng.flat.deliver_grads()
 
 
 class LSTMDecoder(DecoderBase):
@@ -309,3 +365,61 @@ class LSTMDecoder(DecoderBase):
         return decoded, {"score": np.asarray(info["score"], dtype=np.float32), "steps": np.asarray(info["steps"], dtype=np.int64),
                          "n_completed": np.asarray(info["n_completed"], dtype=np.int64),
                          "min_margin": np.asarray(info["min_margin"], dtype=np.float32)}
+
+
+class VarLSTMDecoder(LSTMDecoder):
+    """LSTM decoder with variable-length batching (reference dec_lstm.py:370-476): `x` is a pair (x_, sents_len) of a padded
+    (batch, seq_len) int64 tensor and the sentence lengths; row b is decoded for sents_len[b] - 1 steps and only those steps'
+    token NLL is summed.  Construction follows the reference line by line -- the parent is built, `embed` is replaced by one
+    with padding_idx = vocab['<pad>'], and reset_parameters runs a second time -- so a seed gives the reference's weights; the
+    state_dict keys are the parent's.  The row vocab['<pad>'] of the embedding's gradient is zero (row V - 1 is not special here).
+
+    Lengths: as VarLSTMEncoder's.  A <pad> id INSIDE a sentence (before its length) is outside the envelope: the reference gives
+    such a target weight 0, here it is scored like any other word.  A plain tensor is taken as LSTMDecoder takes it.  The
+    generation methods are inherited.  Exact-f32 configuration only."""
+
+    # True: one length-aware pass over the padded batch; False: every group of equal length through LSTMDecoder's path with
+    # slices of the same noise (A/B runs, tests)
+    masked = True
+
+    def __init__(self, args, vocab, model_init, emb_init):
+        super(VarLSTMDecoder, self).__init__(args, vocab, model_init, emb_init)
+        self.embed = nn.Embedding(len(vocab), args.ni, padding_idx=vocab["<pad>"])
+        vocab_mask = torch.ones(len(vocab))
+        vocab_mask[vocab["<pad>"]] = 0
+        self.loss = nn.CrossEntropyLoss(weight=vocab_mask, reduction="none")
+        self.reset_parameters(model_init, emb_init)
+        self._hip = _eng.LSTMDecoderEngine(self)          # (the parent's engine was built around the embedding replaced above)
+
+    def reconstruct_error(self, x, z, masks=None):
+        """x = (x_ (batch, seq_len) int64, sents_len), z (batch, n_sample, nz) -> (batch, n_sample).  Random draws as the parent's
+        (and the reference's): mask_in (batch, seq_len - 1, ni) per sentence, then mask_out (batch * n_sample, seq_len - 1, nh) per
+        decoder row, seq_len being the longest sentence's length; `masks=(mask_in, mask_out)` injects them."""
+        if torch.is_tensor(x):
+            return super(VarLSTMDecoder, self).reconstruct_error(x, z, masks=masks)
+        x, lengths = _eng.varlen_batch(x)
+        _eng._refuse_bf16_lengths(self._hip)
+        B, T = x.shape
+        if z.dim() != 3 or z.shape[0] != B:
+            raise _lib.LvaeError("the HIP decoder path takes z of shape [B, nsamples, nz]; got %s for a batch of %d" % (tuple(z.shape), B))
+        _eng._same_device("VarLSTMDecoder.reconstruct_error", x.device, z=z)
+        ns = z.size(1)
+        self._hip.ensure(x.device)
+        if masks is None:
+            m_in, m_out = self._draw_masks(B, T - 1, x.device)
+            if ns > 1 and m_out is not None:
+                m_out = torch.empty(B * ns, T - 1, self.nh, device=x.device).bernoulli_(1 - self.dropout_out.p).to(torch.uint8)
+        else:
+            m_in, m_out = masks
+            _eng._same_device("VarLSTMDecoder.reconstruct_error", x.device, mask_in=m_in, mask_out=m_out)
+
+            def cut(m):          # masks drawn for the batch tensor as given: the columns of the cut padding go
+                if m is None:
+                    return None
+                if m.dim() == 3 and m.shape[1] > T - 1:
+                    m = m[:, :T - 1]
+                return m.to(dtype=torch.uint8).contiguous()
+            m_in, m_out = cut(m_in), cut(m_out)
+        fn = _VarDecoderFn if self.masked else _DecoderByLengthFn
+        rec = fn.apply(self._hip, x, z.float().contiguous(), m_in, m_out, self.dropout_in.p, self.dropout_out.p, lengths, *self._params())
+        return rec.view(B, ns)

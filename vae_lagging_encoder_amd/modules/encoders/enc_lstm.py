@@ -29,6 +29,50 @@ class _EncoderFn(torch.autograd.Function):
         return (None, None) + eng.flat.deliver_grads()
 
 
+class _VarEncoderFn(torch.autograd.Function):
+    """_EncoderFn on a padded batch with lengths: the length-aware recurrences (engine.LSTMEncoderEngine.forward(lengths=))."""
+
+    @staticmethod
+    def forward(ctx, eng, x, lengths, *params):
+        mulv = eng.forward(x, lengths=lengths)
+        ctx.eng = eng
+        ctx.gen = eng.gen
+        return mulv.clone()
+
+    @staticmethod
+    def backward(ctx, dmulv):
+        eng = ctx.eng
+        eng.flat.before_autograd_backward()
+        eng.backward(dmulv, ctx.gen)
+        return (None, None, None) + eng.flat.deliver_grads()
+
+
+class _EncoderByLengthFn(torch.autograd.Function):
+    """The A/B route (VarLSTMEncoder.masked = False): every group of equal length through the equal-length engine."""
+
+    @staticmethod
+    def forward(ctx, eng, x, lengths, *params):
+        B = x.shape[0]
+        V, ni, H, nz2 = eng.dims()
+        out = torch.empty(B, nz2, dtype=torch.float32, device=x.device)
+        ctx.groups = _eng.length_groups(lengths)
+        ctx.book = _eng.GroupedBackward(eng)
+        for n, rows in ctx.groups:
+            out[rows] = eng.forward(x[rows, :n].contiguous())
+            ctx.book.after_forward(eng._ws(int(rows.numel()), n))
+        ctx.eng = eng
+        return out
+
+    @staticmethod
+    def backward(ctx, dmulv):
+        eng = ctx.eng
+        eng.flat.before_autograd_backward()
+        for i, (n, rows) in enumerate(ctx.groups):
+            d = dmulv[rows].contiguous()
+            ctx.book.backward(i, lambda: eng._ws(int(rows.numel()), n), lambda gen: eng.backward(d, gen))
+        return (None, None, None) + eng.flat.deliver_grads()
+
+
 class LSTMEncoder(GaussianEncoderBase):
     """Gaussian LSTM encoder with constant-length batching (reference enc_lstm.py:11-64)."""
 
@@ -65,3 +109,28 @@ class LSTMEncoder(GaussianEncoderBase):
         The whole of `input` is embedded, <s> and </s> included."""
         mulv = self._forward_mulv(input)
         return mulv[:, :self.nz], mulv[:, self.nz:]
+
+
+class VarLSTMEncoder(LSTMEncoder):
+    """Gaussian LSTM encoder with variable-length batching (reference enc_lstm.py:77-126): `input` is a pair (x, sents_len) of a
+    padded (batch, seq_len) int64 tensor and the sentence lengths, and mu / logvar come from the LSTM state after each row's own
+    last token.  Same constructor, containers and state_dict keys as LSTMEncoder.  `encode`, `sample`, `eval_inference_dist`
+    and `calc_mi` are the base class's on top of `forward`.
+
+    Lengths count every token of a row, <s> and </s> included (what data.MonoTextData.data_iter / data_sample yield).  Beyond
+    the reference: they need not be sorted, seq_len may exceed the longest sentence, and they may be a list of ints or an
+    integer tensor on any device; a wrong count, a length below 2 or above seq_len raises ValueError before any launch.  A plain
+    (batch, seq_len) tensor is taken as LSTMEncoder takes it.  Exact-f32 configuration only (engine.LvaeError under "bf16")."""
+
+    # True: one length-aware recurrence over the padded batch (lv_lstm_fwd_len_f32 / lv_lstm_bwd_len_f32); False: every group of
+    # equal length through LSTMEncoder's equal-length path, concatenated -- the only route before these kernels (A/B runs, tests)
+    masked = True
+
+    def _forward_mulv(self, input):
+        if torch.is_tensor(input):
+            return super(VarLSTMEncoder, self)._forward_mulv(input)
+        x, lengths = _eng.varlen_batch(input)
+        _eng._refuse_bf16_lengths(self._hip)
+        self._hip.ensure(x.device)
+        fn = _VarEncoderFn if self.masked else _EncoderByLengthFn
+        return fn.apply(self._hip, x, lengths, *self._params())

@@ -76,6 +76,13 @@ class VAE(nn.Module):
         return {"precision": getattr(e, "precision", None), "encoder_forward": "f32" if getattr(e, "exact_forward", ()) else "operands",
                 "forward_operands": getattr(e, "fwd_operands", None)}
 
+    @staticmethod
+    def _batch(x):
+        """A variable-length batch (x, sents_len) -- what VarLSTMEncoder / VarLSTMDecoder take -- in its validated form
+        (engine.varlen_batch: lengths checked and moved to the device ONCE per call, however often the networks are run on it);
+        anything else as it is."""
+        return _eng.varlen_batch(x) if isinstance(x, (tuple, list)) and len(x) == 2 else x
+
     # ---- training path (reference vae.py:35-98) ---------------------------------------------------------
     def encode(self, x, nsamples=1, eps=None):
         """-> z (batch, nsamples, nz), KL (batch,).  `eps` injects the reparameterisation noise."""
@@ -92,6 +99,7 @@ class VAE(nn.Module):
         noise = (eps, mask_in, mask_out) injects the random draws of this call (parity tests); the default draws
         them from torch's device generator at the same three places the reference does."""
         eps, masks = (None, None) if noise is None else (noise[0], (noise[1], noise[2]))
+        x = self._batch(x)
         z, kl = self.encode(x, nsamples, eps=eps)
         dec_extra = {} if masks is None else {"masks": masks}
         rec = self.decoder.reconstruct_error(x, z, **dec_extra).mean(dim=1)
@@ -126,6 +134,7 @@ class VAE(nn.Module):
         vae.py:100-129).  The decoder pass over batch*ns sequences is the hot path's HIP forward; log p(z), log q(z|x) and
         the final log_sum_exp are lv_eval.hip kernels."""
         log_w = []
+        x = self._batch(x)
         for _ in range(int(nsamples / ns)):
             z, stats = self.encoder.sample(x, ns)
             log_w.append(self.eval_complete_ll(x, z) - self.eval_inference_dist(x, z, stats))
@@ -182,6 +191,7 @@ class VAE(nn.Module):
         expanded; no logits)."""
         if self._fused_grid_ok(x, grid_z):
             return self._fused_grid_posterior(x, grid_z, True)[0]
+        x = self._batch(x)
         n = x.size(0) if torch.is_tensor(x) else x[0].size(0)
         joint = self.eval_complete_ll(x, grid_z.unsqueeze(0).expand(n, *grid_z.size()).contiguous())
         return joint - log_sum_exp(joint, dim=1, keepdim=True)
@@ -259,6 +269,7 @@ class VAE(nn.Module):
         if nsamples < 1 or chains < 1 or burn_in < 0 or thin < 1:
             raise ValueError("sample_from_posterior: nsamples >= 1, chains >= 1, burn_in >= 0, thin >= 1 expected")
         total = burn_in + nsamples * thin
+        x = self._batch(x)
         with torch.no_grad():
             dev = x.device if torch.is_tensor(x) else x[0].device
             if noise is not None:
