@@ -213,6 +213,14 @@ int lv_lstm_persist16_pack2(const float* whh, float* wpk_fwd, float* wpk_bwd, in
 int lv_lstm_persist16_pack2_h16(const float* whh, float* wpk_fwd, float* wpk_bwd, int H, void* stream);
 int lv_lstm_fwd_bf16_persist16(const float* gx, const float* wpk, float* hs, float* cs, float* saved, float* xch, int* status,
                                int T, int B, int R, int flags, int H, void* stream);
+/* The persistent forward COMPUTING ITS OWN INPUT PROJECTION (4 rows per group): instead of gx it takes the 16-bit image of the layer
+ * input x16 [T * B][ldx] (bf16; binary16 with flags bit 5), the unit-major 16-bit image of W_ih wih16 [4H][ni] (row 4u + g, same format)
+ * and the projection's unit-major f32 addend -- one row (addend_row_stride = 0) or row b at addend + b * addend_row_stride -- and forms
+ * gx[t][b] = x16[t * B + b] . wih16^T + addend[b] four timesteps at a time in the hand-off wait of the recurrence.  The other
+ * arguments as lv_lstm_fwd_bf16_persist16.  ni = 512, H = 1024 and R <= 4 only: LV_ERR_UNSUPPORTED, nothing launched, otherwise. */
+int lv_lstm_fwd_bf16_persist16_x(const void* x16, long ldx, const void* wih16, int ni, const float* addend, long addend_row_stride,
+                                 const float* wpk, float* hs, float* cs, float* saved, float* xch, int* status,
+                                 int T, int B, int R, int flags, int H, void* stream);
 int lv_lstm_bwd_bf16_persist16(const float* dh_ext, const float* dh_last, const float* wpk, const float* saved, const float* hs,
                                const float* cs, uint16_t* dG16, float* dGsum, float* xch, int* status, float* dh0, float* dc0,
                                int tanh_init, int T, int B, int R, int flags, int H, void* stream);

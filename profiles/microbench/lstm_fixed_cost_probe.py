@@ -27,6 +27,29 @@ def t(f, n=20):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
+if "--fused-gx" in sys.argv:
+    # the forward that forms its own input projection (lv_lstm_fwd_bf16_persist16_x) next to the Gx form, T = 40 / 200, 4 rows,
+    # alternating exchange halves: fixed + per-timestep cost of each from the two lengths
+    NI = 512
+    W16 = ((torch.rand(4 * H, NI, device=dev) * 2 - 1) * 0.03).to(torch.bfloat16).view(torch.int16)
+    add = torch.randn(B, 4 * H, device=dev) * 0.1
+    FF = lambda: 1 | _xch_flags(wi, "f", R, "cpu")
+    res = {}
+    for T in (40, 200):
+        gx = torch.randn(T, B, 4 * H, device=dev) * 0.5
+        X16 = torch.randn(T * B, NI, device=dev).to(torch.bfloat16).view(torch.int16)
+        hs = torch.zeros(T + 1, B, H, device=dev); cs = torch.zeros(T + 1, B, H, device=dev)
+        saved = torch.empty(lib.lv_lstm_persist16_saved_floats(T, R), device=dev)
+        res[T] = (t(lambda: lib.lv_lstm_fwd_bf16_persist16(P(gx), P(wf), P(hs), P(cs), P(saved), P(xch), P(st), T, B, R, FF(), H, s)),
+                  t(lambda: lib.lv_lstm_fwd_bf16_persist16_x(P(X16), NI, P(W16), NI, P(add), 4 * H, P(wf), P(hs), P(cs), P(saved), P(xch),
+                                                             P(st), T, B, R, FF(), H, s)))
+        print("T=%3d: forward reading Gx %7.1f us, forming Gx itself %7.1f us (back-to-back launches)" % (T, res[T][0], res[T][1]))
+    for name, col in (("reading Gx", 0), ("forming Gx", 1)):
+        b = (res[200][col] - res[40][col]) / 160.0
+        print("%s: fixed %.1f us per launch + %.3f us per timestep" % (name, res[40][col] - 40 * b, b))
+    print("status", int(st.item()))
+    sys.exit(0)
+
 Ts = [1, 2, 4, 8, 16, 50, 100, 200]
 rows = []
 for mode in ("memset", "alternating halves"):

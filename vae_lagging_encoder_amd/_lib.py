@@ -85,6 +85,7 @@ SIGNATURES = {
     "lv_lstm_persist16_pack2": [_vp, _vp, _vp, _i, _vp],
     "lv_lstm_persist16_pack2_h16": [_vp, _vp, _vp, _i, _vp],
     "lv_lstm_fwd_bf16_persist16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "lv_lstm_fwd_bf16_persist16_x": [_vp, _l, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "lv_lstm_bwd_bf16_persist16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "lv_transpose_f32": [_vp, _vp, _i, _i, _vp],
     "lv_transpose_ld_f32": [_vp, _l, _vp, _l, _i, _i, _vp],

@@ -236,6 +236,10 @@ static inline f32x4 lv_mfma_16x16x32_f16_areg(uint4 a, uint4 b, f32x4 c) {
     return d;
 }
 static inline f32x4 lv_mfma_16x16x32_f16_areg_first(uint4 a, uint4 b) { return lv_mfma_16x16x32_f16_areg(a, b, f32x4{0.f, 0.f, 0.f, 0.f}); }
+template <bool F16> static inline f32x4 lv_mfma_16x16x32_vreg(uint4 a, uint4 b, f32x4 c) {
+    return F16 ? lv_mfma_16x16x32_f16_areg(a, b, c) : lv_emu_mfma_16x16x32_bf16(a, b, c);
+}
+template <bool F16> static inline f32x4 lv_mfma_16x16x32_vreg_first(uint4 a, uint4 b) { return lv_mfma_16x16x32_vreg<F16>(a, b, f32x4{0.f, 0.f, 0.f, 0.f}); }
 #else
 #include <hip/hip_runtime.h>
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -336,6 +340,24 @@ __device__ __forceinline__ f32x4 lv_mfma_16x16x32_f16_areg_first(uint4 a, uint4 
     const lv_u32x4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
     f32x4 c;
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=v"(c) : "a"(av), "v"(bv));
+    return c;
+}
+// 16x16x32 (bf16 / binary16) with EVERY operand in VGPRs, as inline assembly under the same rules (LV_MFMA_DRAIN / LV_MFMA_RESULT): for a
+// second, small product inside a kernel whose AGPRs are full of resident weights.  Through the builtin the allocator may give the
+// accumulators AGPRs and move resident weights out to VGPRs, with v_accvgpr_write copies right in front of the _areg instructions
+// the hazard recognizer cannot see into (first build of the persistent forward's input projection: one column block of the
+// recurrent product read its weights before the copy had landed).
+template <bool F16> __device__ __forceinline__ f32x4 lv_mfma_16x16x32_vreg(uint4 a, uint4 b, f32x4 c) {
+    const lv_u32x4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
+    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
+    return c;
+}
+template <bool F16> __device__ __forceinline__ f32x4 lv_mfma_16x16x32_vreg_first(uint4 a, uint4 b) {
+    const lv_u32x4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+    f32x4 c;
+    if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
+    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
     return c;
 }
 #define LV_MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 3" ::: "memory")

@@ -140,6 +140,9 @@ struct Fwd16P {
     int* status;
     int T, B, R;
     uint4* clr; long clr_n;     // double-buffered exchange (flags bit 1): the OTHER half, zeroed by this launch for the next one (clr_n uint4s)
+    // XIN (the forward computes its own input projection; gx is not read): the 16-bit image of the layer input, rows [T * B] of
+    // ldx elements; the unit-major 16-bit image of W_ih [4H][XNI]; the per-(row, unit) addend, unit-major, row b at add + b * add_ld
+    const uint16_t* x16; long ldx; const uint16_t* wih; const float* add; long add_ld;
 };
 
 // Zero `n` uint4s, the whole grid sharing the work (the first thing a persistent launch does, before a group without rows leaves):
@@ -168,8 +171,30 @@ struct __attribute__((aligned(16))) Fwd16Lds {
     int abort;
 };
 
-template <int RP, bool LOCAL, bool F16 = false>
+// XIN: the 4-row forward that computes Gx = X . W_ih^T itself, four timesteps at a time, in the hand-off wait of the recurrence.
+// At 4 rows per group the 16 B-columns of the 16x16x32 tile are 4 timesteps x 4 rows of the layer input, so ONE pass of the
+// workgroup's 128 gate columns of W_ih over [x_{t0} .. x_{t0 + 3}] at full tile utilisation is the input projection of a whole
+// PASS of four steps: 32 MFMAs per wave (column blocks 2w, 2w + 1 over the full K = XNI, no cross-wave sum) that need no result
+// of the recurrence.  The slice of W_ih (128 KB) stays resident in MFMA-fragment order, XKL of its 16 k-steps in LDS (each wave
+// reads back only what it wrote: linear ds_read_b128) and the others in VGPRs.
+constexpr int XNI = 512;                // input width the XIN forward is built for
+constexpr int XKS = XNI / 32;           // k-steps of the mini-product
+#ifndef LV_XIN_KS_LDS
+#define LV_XIN_KS_LDS 12                // k-steps of the W_ih slice kept in LDS (96 KB); the other 4 sit in 32 VGPRs per lane
+#endif
+constexpr int XKL = LV_XIN_KS_LDS;
+constexpr int XS_PITCH = XNI / 8 + 2;   // 16-byte slots per column of the staged input rows (66: = 2 mod 16)
+struct __attribute__((aligned(16))) Fwd16XLds : Fwd16Lds<4> {
+    uint4 wih[4][XKL][2][64];           // [wave][ks][column block 2w + j][lane]: A fragments of the wave's 32 gate columns
+    uint4 xs[16 * XS_PITCH];            // the pass being multiplied: column c = 4 (step in pass) + row, XNI 16-bit elements
+    f32x4 rb[2][16][RED_SLOTS];         // [pass parity][column c][unit of the workgroup]: the (i, f, g, o) projections of one pass
+};
+template <bool C, class A, class B> struct lv_pick_t { typedef A type; };
+template <class A, class B> struct lv_pick_t<false, A, B> { typedef B type; };
+
+template <int RP, bool LOCAL, bool F16 = false, bool XIN = false>
 __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
+    static_assert(!XIN || RP == 4, "the fused input projection maps the tile's 16 columns to 4 steps x 4 rows");
     // LOCAL: hand-off stores without the agent-scope write-through (lv_xcd_store_u64): valid while a group's 32 workgroups share an XCD
     // F16: the recurrent operands -- the register image of W_hh and the h granules -- are IEEE binary16 and the products run on
     // v_mfma_f32_16x16x32_f16: the same kernel at 11 instead of 8 bits of significand for the WEIGHTS, whose rounding acts at every
@@ -178,7 +203,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
     auto h16 = [](float v) -> uint32_t { return F16 ? (uint32_t)lv_f32_to_f16_bits(v) : lv_f32_to_bf16_bits(v); };
     auto put = [](gran_t* q, gran_t v) { if (LOCAL) lv_xcd_store_u64(q, v); else gran_store(q, v); };
     constexpr int NP = Cfg16<RP>::NP, SBK = Cfg16<RP>::SBK, GJ = Cfg16<RP>::GJ;
-    LV_BLOCK_SHARED(Fwd16Lds<RP>, sm);
+    typedef typename lv_pick_t<XIN, Fwd16XLds, Fwd16Lds<RP>>::type Lds;
+    LV_BLOCK_SHARED(Lds, sm);
     int& s_abort = sm.abort;
     const int tid = (int)threadIdx.x, l = tid & 63, w = tid >> 6;
     const int group = (int)blockIdx.x % PGROUPS, member = (int)blockIdx.x / PGROUPS;
@@ -189,6 +215,21 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
     clear_other_half(p.clr, p.clr_n);
     if (rows == 0) return;                                    // a group without rows leaves its XCD to whoever else wants it
     if (tid == 0) s_abort = 0;
+    const int kq = l >> 4;
+
+    // XIN: the wave's part of the W_ih slice, permuted into fragment order on the way in.  Lane (c = l & 15, kq) of fragment
+    // (ks, j) holds the 8 weights k = 32 ks + 8 kq + e of gate column 128 member + 16 (2w + j) + c = row 4u + g of the image.
+    uint4 xwr[XIN ? XKS - XKL : 1][2];
+    if constexpr (XIN) {
+        const uint16_t* wb = p.wih + (long)(128 * member + 32 * w + (l & 15)) * XNI + 8 * kq;
+#pragma unroll
+        for (int ks = 0; ks < XKS; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint4 v = *reinterpret_cast<const uint4*>(wb + (long)(16 * j) * XNI + 32 * ks);
+                if (ks < XKL) sm.wih[w][ks][j][l] = v; else xwr[ks - XKL][j] = v;
+            }
+    }
 
     uint4 wreg[8][8];                                         // [ks][nb]: 256 VGPRs, resident for the whole call
     {
@@ -239,10 +280,17 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
         if (own[q] && even) put(hx_g + (long)prow[q] * (PH / 2) + (punit >> 1), ((gran_t)1u << 32) | (gran_t)(mine | (next << 16)));
     }
 
-    float4 gxb[NP][SBK];
+    float4 gxb[XIN ? 1 : NP][XIN ? 1 : SBK];
+    f32x4 addv[NP];                                           // XIN: the projection's addend of the pair, constant over t
+    if constexpr (XIN) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q)
+            addv[q] = *reinterpret_cast<const f32x4*>(p.add + (long)(b0 + (own[q] ? prow[q] : 0)) * p.add_ld + 4 * punit);
+    }
     f32x4 recb[NP][SBK];
     float cb[NP][SBK], hb[NP][SBK];
     auto load_slots = [&](int tb, int lo, int hi) {          // gx of steps tb + [lo, hi) into their slots
+        if constexpr (XIN) return;
 #pragma unroll
         for (int q = 0; q < NP; ++q)
 #pragma unroll
@@ -271,12 +319,74 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
                 }
             }
     };
+    // XIN, one PASS = the four steps t0 .. t0 + 3 (t0 a multiple of 4).  x_load: wave w fetches row w of the slice at the pass's
+    // four steps (1 KB per instruction) -- unconditional, from clamped addresses like load_slots: rows the slice does not have
+    // read its row 0, steps >= T read step T - 1.  x_stage puts them into LDS as the B operand image, x_product multiplies: lane
+    // (c, kq) of the D tile of column block nb holds the (i, f, g, o) of unit 4 nb + kq for column c = one gx record.
+    // Schedule of pass P + 1 inside pass P: loads behind the gather of step 0, staging behind the gather of step 2 (in front of
+    // that step's barrier), product behind the publish of step 3, into rb[(P + 1) & 1].  The readers of that record buffer (pass
+    // P - 1) and of xs (the product of pass P) are separated from these writes by the barriers of steps 0 / 0 and 1 of pass P.
+    f32x4 xr[XIN ? 4 : 1];                                     // (16 bytes of raw bits each: moved, never computed on)
+    auto x_load = [&](int t0) {
+        if constexpr (XIN) {
+            const int r = w < rows ? w : 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int t = t0 + j < T ? t0 + j : T - 1;
+                xr[j] = *reinterpret_cast<const f32x4*>(p.x16 + ((long)t * B + b0 + r) * p.ldx + 8 * l);
+            }
+        }
+    };
+    auto x_stage = [&]() {
+        if constexpr (XIN) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(&sm.xs[(4 * j + w) * XS_PITCH + l]) = xr[j];
+        }
+    };
+    auto x_product = [&](int par) {
+        if constexpr (XIN) {
+            // (all operands in VGPRs, the accumulators too: the AGPRs belong to W_hh -- lv_mfma_16x16x32_vreg)
+            f32x4 a0, a1;
+            const uint4* xb = sm.xs + (l & 15) * XS_PITCH + kq;
+            // the fragment reads run two k-steps ahead of their MFMAs (an LDS round trip is about two k-steps of matrix-pipe time)
+            uint4 bf[XKS], w0[XKS], w1[XKS];
+            auto frag = [&](auto KS) {
+                constexpr int ks = decltype(KS)::value;
+                if constexpr (ks < XKS) {
+                    bf[ks] = xb[4 * ks];
+                    if constexpr (ks < XKL) { w0[ks] = sm.wih[w][ks][0][l]; w1[ks] = sm.wih[w][ks][1][l]; }
+                    else { w0[ks] = xwr[ks - XKL][0]; w1[ks] = xwr[ks - XKL][1]; }
+                }
+            };
+            auto step = [&](auto KS) {
+                constexpr int ks = decltype(KS)::value;
+                frag(lv_const<ks + 2>());
+                LV_SCHED_BARRIER();
+                a0 = ks == 0 ? lv_mfma_16x16x32_vreg_first<F16>(w0[ks], bf[ks]) : lv_mfma_16x16x32_vreg<F16>(w0[ks], bf[ks], a0);
+                a1 = ks == 0 ? lv_mfma_16x16x32_vreg_first<F16>(w1[ks], bf[ks]) : lv_mfma_16x16x32_vreg<F16>(w1[ks], bf[ks], a1);
+            };
+            static_assert(XKS == 16, "sixteen k-steps, written out");
+            frag(lv_const<0>()); frag(lv_const<1>());
+            step(lv_const<0>()); step(lv_const<1>()); step(lv_const<2>()); step(lv_const<3>());
+            step(lv_const<4>()); step(lv_const<5>()); step(lv_const<6>()); step(lv_const<7>());
+            step(lv_const<8>()); step(lv_const<9>()); step(lv_const<10>()); step(lv_const<11>());
+            step(lv_const<12>()); step(lv_const<13>()); step(lv_const<14>()); step(lv_const<15>());
+            LV_MFMA_DRAIN();
+            LV_MFMA_RESULT(a0);
+            LV_MFMA_RESULT(a1);
+            f32x4* rd = sm.rb[par][l & 15];
+            rd[8 * w + kq] = a0;                               // column block 2w: units 8w + kq
+            rd[8 * w + 4 + kq] = a1;                           // column block 2w + 1
+        }
+    };
     load_slots(0, 0, SBK);
+    x_load(0);
+    x_stage();
     __syncthreads();
+    x_product(0);                                              // (its readers wait at the barrier of step 0)
 
     const int nq = rows * 128;                                 // granules of this wave's K quarter
     const int brow = (l & 15) < rows ? (l & 15) : 0;           // batch row of this lane's B fragments (rows beyond the slice re-read row 0)
-    const int kq = l >> 4;
     uint32_t abl_keep[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // (LV_P16_ABL bit 4 only)
     for (int tb = 0; tb < T; tb += SBK) {
 #pragma unroll
@@ -366,6 +476,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
             // step: the next block's other slots.
             if (s2 == 0 && tb > 0) { store_block(tb - SBK); load_slots(tb, SBK - 1, SBK); }
             if (s2 == SBK - 1) load_slots(tb + SBK, 0, SBK - 1);
+            if ((s2 & 3) == 0) x_load(t + 4);
+            if ((s2 & 3) == 2) x_stage();
             LV_TRACE_MARK(t, 1);
             LV_WAIT_LDS();                                     // the wave reads back only what its own lanes wrote
             LV_TRACE_MARK(t, 2);
@@ -419,7 +531,12 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
                 if (own[q]) {
                     const f32x4 q0 = sm.red[t & 1][0][prow[q]][uw], q1 = sm.red[t & 1][1][prow[q]][uw];
                     const f32x4 q2 = sm.red[t & 1][2][prow[q]][uw], q3 = sm.red[t & 1][3][prow[q]][uw];
-                    const float4 gxv = gxb[q][s2];
+                    float4 gxv;
+                    if constexpr (XIN) {
+                        const f32x4 xv = sm.rb[(t >> 2) & 1][4 * (t & 3) + prow[q]][uw];
+                        gxv = make_float4(xv[0] + addv[q][0], xv[1] + addv[q][1], xv[2] + addv[q][2], xv[3] + addv[q][3]);
+                    } else
+                        gxv = gxb[q][s2];
                     auto sg_ = [](float x) { return (LV_P16_ABL & 4) ? 0.5f + 0.25f * x : lv_sigmoid_fast(x); };
                     auto th_ = [](float x) { return (LV_P16_ABL & 4) ? 0.9f * x : lv_tanh_fast(x); };
                     const float ig = sg_(gxv.x + ((q0[0] + q1[0]) + (q2[0] + q3[0])));
@@ -439,6 +556,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
                     put(hx_g + (long)((t + 1) & 1) * hx_par + (long)prow[q] * (PH / 2) + (punit >> 1),
                         ((gran_t)(uint32_t)(t + 2) << 32) | (gran_t)(mine | (next << 16)));
             }
+            if ((s2 & 3) == 3) x_product(((t + 1) >> 2) & 1);
             LV_TRACE_MARK(t, 5);
         }
     }
@@ -1024,6 +1142,44 @@ extern "C" int lv_lstm_fwd_bf16_persist16(const float* gx, const float* wpk, flo
         if (R <= 4) LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<4, false>), grid, block, 0, stream, p);
         else if (R <= 8) LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<8, false>), grid, block, 0, stream, p);
         else LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<16, false>), grid, block, 0, stream, p);
+    }
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// The same recurrence computing its own input projection (the XIN form of the kernel, 4 rows per group): instead of gx it takes
+// the 16-bit image of the layer input x16 [T * B][ldx] (bf16, or binary16 with flags bit 5), the unit-major 16-bit image of W_ih
+// wih16 [4H][ni] (row 4u + g; same format) and the projection's unit-major f32 addend -- one row (addend_row_stride = 0: the
+// biases) or row b at addend + b * addend_row_stride (the decoder's z projection) -- and forms
+// gx[t][b][4u + g] = x16[t * B + b] . wih16[4u + g] + addend[b][4u + g] four timesteps at a time inside the launch.  Everything
+// else (wpk, hs, cs, saved, xch, status, flags) as lv_lstm_fwd_bf16_persist16.  Takes ni = 512, H = 1024, R <= 4 only and
+// returns LV_ERR_UNSUPPORTED, launching nothing, for any other shape.
+extern "C" int lv_lstm_fwd_bf16_persist16_x(const void* x16, long ldx, const void* wih16, int ni, const float* addend,
+                                            long addend_row_stride, const float* wpk, float* hs, float* cs, float* saved, float* xch,
+                                            int* status, int T, int B, int R, int flags, int H, void* stream) {
+    if (!x16 || !wih16 || !addend || !wpk || !hs || !cs || !saved || !xch || !status) return LV_ERR_ARG;
+    if (T < 0 || B <= 0 || H <= 0 || ni <= 0 || ldx < ni || addend_row_stride < 0) return LV_ERR_SHAPE;
+    if (H != PH || ni != XNI || !check_R(B, R) || R > 4) return LV_ERR_UNSUPPORTED;
+    if (addend_row_stride != 0 && addend_row_stride < 4 * PH) return LV_ERR_SHAPE;
+    if ((((uintptr_t)wpk) & 15) != 0 || (((uintptr_t)saved) & 15) != 0 || (((uintptr_t)xch) & 15) != 0 || (((uintptr_t)x16) & 15) != 0 ||
+        (((uintptr_t)wih16) & 15) != 0 || (((uintptr_t)addend) & 15) != 0 || (ldx & 7) != 0 || (addend_row_stride & 3) != 0)
+        return LV_ERR_ALIGN;
+    if (lv_device_cus() < PGROUPS * PMEMBERS) return LV_ERR_UNSUPPORTED;
+    if (T == 0) return LV_OK;
+    char* const xb = reinterpret_cast<char*>(xch);
+    const int dbl = (flags >> 1) & 1, half = dbl ? (flags >> 2) & 1 : 0;
+    gran_t* hx = reinterpret_cast<gran_t*>(xb + XCH_FWD_OFF[half]);
+    if (!dbl) (void)hipMemsetAsync(hx, 0, (size_t)XCH_FWD16_BYTES, (hipStream_t)stream);
+    Fwd16P p{nullptr, reinterpret_cast<const uint4*>(wpk), hs, cs, saved, hx, status, T, B, R,
+             dbl ? reinterpret_cast<uint4*>(xb + XCH_FWD_OFF[1 - half]) : nullptr, XCH_FWD16_BYTES / 16,
+             static_cast<const uint16_t*>(x16), ldx, static_cast<const uint16_t*>(wih16), addend, addend_row_stride};
+    const dim3 grid(PGROUPS * PMEMBERS), block(256);
+    if (flags & 32) {
+        if (flags & 1) LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<4, true, true, true>), grid, block, 0, stream, p);
+        else LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<4, false, true, true>), grid, block, 0, stream, p);
+    } else {
+        if (flags & 1) LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<4, true, false, true>), grid, block, 0, stream, p);
+        else LV_LAUNCH_RESIDENT((lstm_fwd_persist_k16_kernel<4, false, false, true>), grid, block, 0, stream, p);
     }
     LV_CHECK_LAUNCH();
     return LV_OK;

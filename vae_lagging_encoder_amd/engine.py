@@ -495,6 +495,35 @@ def _persistent_ok(eng, img, B, H, device, max_b):
             and torch.device(device).type == "cuda" and torch.cuda.get_device_properties(device).multi_processor_count >= 256)
 
 
+# The 4-row persistent forward computes its own input projection (lv_lstm_fwd_bf16_persist16_x: no Gx product, no Gx buffer);
+# LVAE_FUSED_GX=0: the projection GEMM + Gx path, for A/B measurements.  FUSED_GX_ENC / FUSED_GX_DEC decide the two layers apart.
+FUSED_GX = os.environ.get("LVAE_FUSED_GX", "1") != "0"
+FUSED_GX_ENC = True
+FUSED_GX_DEC = True
+_FUSED_GX_NI = 512       # the input width lv_lstm_fwd_bf16_persist16_x is built for
+
+
+def _fused_gx_ok(eng, img, B, H, ni, device, layer_on):
+    """The forward of this layer runs as the persistent launch that forms Gx itself: the persistent path is on (any demotion
+    down the ladder turns this off with it, and the caller computes Gx as before), the shape is the kernel's (ni = 512, <= 4 rows
+    per group), and the engine does not belong to a hipGraph trainer (ws_evictable False: its workspaces are pinned and its eager
+    warm-up steps must run what the captured ones will) nor is the launch being captured (captured steps keep the GEMM + Gx path)."""
+    if not (FUSED_GX and layer_on and ni == _FUSED_GX_NI and eng.ws_evictable and _persistent_ok(eng, img, B, H, device, _PERSIST_MAX_B)):
+        return False
+    if _persist_rows(eng, B) > 4:
+        return False
+    return not (torch.cuda.is_current_stream_capturing() or (eng._wimg is not None and getattr(eng._wimg, "xstate", {}).get("captured")))
+
+
+def _gx_buffer(c, w, rows, H):
+    """w.Gx [rows][4H] f32, allocated when a path that materialises the input projection first runs (the fused forward never does:
+    2 x 105 MB at the Yahoo shape)."""
+    if w.Gx is None:
+        w.Gx = c.f32(rows, 4 * H)
+        c.grew(w.ws_key, rows * 4 * H * 4)
+    return w.Gx
+
+
 def weights_version(eng):
     """Changes whenever the module's weights may have changed: in-place torch updates bump the parameters' version
     counters (optimizer.step, load_state_dict, user edits), raw-pointer updates by the fused trainer bump eng.wgen."""
@@ -696,10 +725,14 @@ def _same_device(what, dev, **operands):
             raise _lib.LvaeError("%s: %s is on %s, x on %s" % (what, name, t.device, dev))
 
 
-def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, device, steps=None):
+def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, device, steps=None, xin=None):
     """The forward recurrence of one LSTM layer: exact f32, bf16 launch-per-step, or (bf16 image path on a >= 256-CU
     device, H = 1024, B <= 128) the single persistent launch of lv_lstm_persist16.hip.  steps = (int32 [B] on the device,
-    their maximum): the length-aware exact-f32 recurrence (lv_lstm_fwd_len_f32), row b active while t < steps[b]."""
+    their maximum): the length-aware exact-f32 recurrence (lv_lstm_fwd_len_f32), row b active while t < steps[b].
+    xin = (addend, addend_row_stride) from _LstmImages.forward(product=False): no Gx exists, the persistent launch forms it from
+    img.X and the unit-major image of W_ih (the caller asked _fused_gx_ok first)."""
+    if xin is not None and not (steps is None and _persistent_ok(eng, img, B, H, device, _PERSIST_MAX_B)):
+        raise _lib.LvaeError("the fused input projection exists in the persistent forward only")
     args = (Gx, whh, P(w.hs), P(w.cs), P(w.gates), mask, scale, hdrop)
     w.saved_layout = ("canonical", T, B, 0)
     if steps is not None:
@@ -717,8 +750,12 @@ def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, dev
         need = lib.lv_lstm_persist16_saved_floats(T, rows)
         if w.gates.numel() < need:              # eng.persist_rows / eng.persistent changed after the workspace was built
             w.gates = torch.empty(need, dtype=torch.float32, device=w.gates.device)
-        lib.lv_lstm_fwd_bf16_persist16(Gx, P(wi.fwd16), P(w.hs), P(w.cs), P(w.gates), P(wi.xch), P(eng.status), T, B, rows,
-                                       eng.persist_flags | _xch_flags(wi, "f", rows, device, T) | (32 if getattr(wi, "h16", False) else 0), H, s)
+        flags = eng.persist_flags | _xch_flags(wi, "f", rows, device, T) | (32 if getattr(wi, "h16", False) else 0)
+        if xin is not None:
+            lib.lv_lstm_fwd_bf16_persist16_x(P(img.X), img.ni, P(wi.W), img.ni, xin[0], xin[1], P(wi.fwd16), P(w.hs), P(w.cs),
+                                             P(w.gates), P(wi.xch), P(eng.status), T, B, rows, flags, H, s)
+        else:
+            lib.lv_lstm_fwd_bf16_persist16(Gx, P(wi.fwd16), P(w.hs), P(w.cs), P(w.gates), P(wi.xch), P(eng.status), T, B, rows, flags, H, s)
         w.saved_layout = ("persist16", T, B, rows)      # what w.gates holds now: the BPTT must be given the same T, B, R
     else:
         lib.lv_lstm_fwd_bf16_ug(*args, P(w.lstm_ws), T, B, H, s)
@@ -816,11 +853,13 @@ class _LstmImages(object):
     def usable(precision, native16, ni, H):
         return precision == "bf16" and native16 and ni % 8 == 0 and H % 8 == 0
 
-    def forward(self, lib, s, X, W16, Gx, add_a, add_b, rows, wsc, addend_um=None, gather=None, h16=False):
+    def forward(self, lib, s, X, W16, Gx, add_a, add_b, rows, wsc, addend_um=None, gather=None, h16=False, product=True):
         """Gx[r][4u + g] = X[r] . W_ih[g*H + u] + (add_a + add_b)[r % rows][g*H + u]; W16: the unit-major bf16 image of W_ih
         (engine-level, _weight_images); add_a/add_b: gate-major [rows][4H] (add_b may be None), or addend_um: the addend
         already in unit-major order.  gather = (emb, ids, ids_stride, keep, kscale, T, B, V): the layer input is an embedding
-        lookup (+ dropout) -- its bf16 images are gathered straight from the table (lv_embed_gather_b16) and X (f32) is not read."""
+        lookup (+ dropout) -- its bf16 images are gathered straight from the table (lv_embed_gather_b16) and X (f32) is not read.
+        product = False: the images and the addend are built but no product is launched and Gx is not touched; returns
+        (addend pointer, its row stride in floats -- 0: one row) for the forward that forms Gx itself (_lstm_forward's xin)."""
         TB, ni, H = self.TB, self.ni, self.H
         if addend_um is not None:
             addend = addend_um
@@ -836,6 +875,8 @@ class _LstmImages(object):
             emb, ids, ids_stride, keep, kscale, T, B, V = gather
             assert keep is None
             lib.lv_cvt_h16_f32(emb, ni, TB, ni, 0, ids, ids_stride, B, V, P(self.X), ni, P(self.XT), self.ldr, s)
+            if not product:
+                return addend, 4 * H if rows > 1 else 0
             ws = _gemm_ws(lib, s)
             with _prof("gemm_bf16", 2.0 * TB * 4 * H * ni):
                 lib.lv_gemm_h16(TB, 4 * H, ni, 1.0, P(self.X), ni, W16, ni, Gx, 4 * H, 0, addend, 4 * H if rows > 1 else 0, rows, None, 0, 1,
@@ -846,6 +887,8 @@ class _LstmImages(object):
             lib.lv_embed_gather_b16(emb, ids, ids_stride, keep, kscale, T, B, ni, V, P(self.X), ni, P(self.XT), self.ldr, s)
         else:
             lib.lv_cvt_bf16_f32(X, ni, TB, ni, P(self.X), ni, P(self.XT), self.ldr, s)
+        if not product:
+            return addend, 4 * H if rows > 1 else 0
         _gemm16(lib, s, 0, TB, 4 * H, ni, P(self.X), ni, W16, ni, Gx, 4 * H,
                 add1=addend, ld1=4 * H if rows > 1 else 0, mod1=rows)
 
@@ -1072,7 +1115,7 @@ class LSTMEncoderEngine(object):
         def build():
             w = _NS()
             w.X = c.f32(T * B, ni)
-            w.Gx = c.f32(T * B, 4 * H)
+            w.Gx, w.ws_key = None, (B, T)   # _gx_buffer: only where the input projection is materialised
             # index 0 = the initial state: zero for the encoder (enc_lstm.py:60), and no kernel ever writes slot 0
             w.hs = torch.zeros(T + 1, B, H, dtype=torch.float32, device=c.device)
             w.cs = torch.zeros(T + 1, B, H, dtype=torch.float32, device=c.device)
@@ -1125,6 +1168,11 @@ class LSTMEncoderEngine(object):
         self._sort = _sorted_tokens(self, lib, s, x, x_key, T, T, B, V, w)
         biases = dict(add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
         gx_unit_major = True
+        xin = None
+        fuse_gx = (img is not None and not exact and steps is None and getattr(self, "gx_round", None) is None
+                   and _fused_gx_ok(self, img, B, H, ni, x.device, FUSED_GX_ENC))
+        if not fuse_gx:
+            _gx_buffer(self.wsc, w, T * B, H)
         if split:
             self._exact_forward_split(lib, s, img, w, x, T, B, V, ni, H)
         elif img is not None and "gx" in exact:
@@ -1142,8 +1190,8 @@ class LSTMEncoderEngine(object):
                 gx_unit_major = True
         elif img is not None:
             wi = self.refresh_weight_images(B, x.device)
-            img.forward(lib, s, None, P(wi.W), P(w.Gx), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]), 1, self.wsc,
-                        gather=(P(v["embed.weight"]), P(x), T, None, 1.0, T, B, V), h16=self._h16_now)
+            xin = img.forward(lib, s, None, P(wi.W), None if fuse_gx else P(w.Gx), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]), 1,
+                              self.wsc, gather=(P(v["embed.weight"]), P(x), T, None, 1.0, T, B, V), h16=self._h16_now, product=not fuse_gx)
         else:
             _gemm(lib, s, 0, 1, T * B, 4 * H, ni, P(w.X), ni, P(v["lstm.weight_ih_l0"]), ni, P(w.Gx), 4 * H,
                   prec=self.precision, **biases)
@@ -1158,7 +1206,8 @@ class LSTMEncoderEngine(object):
             self._exact_recurrence(lib, s, img, w, gx_unit_major, T, B, H, x.device)
         else:
             with _prof("lstm_fwd_enc", float(T), 1 if _persistent_ok(self, img, B, H, x.device, _PERSIST_MAX_B) else T):
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, T, B, H, x.device, steps=steps)
+                _lstm_forward(self, lib, s, img, w, None if fuse_gx else P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, T, B, H,
+                              x.device, steps=steps, xin=xin)
         if head is not None and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
             eps, z, kl = head
             _gemm(lib, s, 0, 1, B, nz2, H, P(w.hs, T * B * H), H, P(v["linear.weight"]), H, P(w.mulv), nz2)
@@ -1433,7 +1482,7 @@ class LSTMDecoderEngine(object):
                 w.x_rep = torch.empty(Bd, Td + 1, dtype=torch.int64, device=c.device)     # token ids in decoder row order
                 w.Zp_um = c.f32(Bd, 4 * H)             # Zp in unit-major order where the GEMM-based init produced it gate-major
             w.Zp = c.f32(Bd, 4 * H)
-            w.Gx = c.f32(Td * Bd, 4 * H)
+            w.Gx, w.ws_key = None, key      # _gx_buffer: only where the input projection is materialised
             w.hs = c.f32(Td + 1, Bd, H)
             w.cs = c.f32(Td + 1, Bd, H)
             w.gates = c.f32(_saved_floats(self, Td, Bd, H))
@@ -1582,6 +1631,11 @@ class LSTMDecoderEngine(object):
             lib.lv_tanh_f32(P(w.cs), P(w.hs), Bd * H, s)
             _gemm(lib, s, 0, 1, Bd, 4 * H, nz, P(z2), nz, P(wih, ni), ni + nz, P(w.Zp), 4 * H,
                   add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
+        xin = None
+        fuse_gx = (ns == 1 and img is not None and steps is None and _fused_gx_ok(self, img, Bd, H, ni, x.device, FUSED_GX_DEC)
+                   and self._b16(Bd, Td, ns) is not None)
+        if not fuse_gx:
+            _gx_buffer(self.wsc, w, Td * Bd, H)
         if ns > 1:
             zp = w.Zp
             if img is not None and not fused:             # the image path's recurrences read Gx unit-major (4u + g)
@@ -1595,10 +1649,11 @@ class LSTMDecoderEngine(object):
             lib.lv_gx_expand_add_f32(P(w.Gxw), P(zp), P(w.Gx), Td, B, ns, 4 * H, s)
         elif img is not None:
             wi = self.refresh_weight_images(B, x.device)
+            gxp = None if fuse_gx else P(w.Gx)
             if fused:
-                img.forward(lib, s, None, P(wi.W), P(w.Gx), None, None, B, self.wsc, addend_um=P(w.Zp), gather=gather)
+                xin = img.forward(lib, s, None, P(wi.W), gxp, None, None, B, self.wsc, addend_um=P(w.Zp), gather=gather, product=not fuse_gx)
             else:
-                img.forward(lib, s, None, P(wi.W), P(w.Gx), P(w.Zp), None, B, self.wsc, gather=gather)
+                xin = img.forward(lib, s, None, P(wi.W), gxp, P(w.Zp), None, B, self.wsc, gather=gather, product=not fuse_gx)
         else:
             _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(wih), ni + nz, P(w.Gx), 4 * H,
                   add1=P(w.Zp), ld1=4 * H, mod1=B, prec=self.precision)
@@ -1608,7 +1663,8 @@ class LSTMDecoderEngine(object):
         late_mask = b16 is not None and _persistent_ok(self, img, Bd, H, x.device, _PERSIST_MAX_B)
         with _prof("lstm_fwd_dec", float(Td), 1 if _persistent_ok(self, img, Bd, H, x.device, _PERSIST_MAX_B) else Td):
             if late_mask:
-                _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, Bd, H, x.device)
+                _lstm_forward(self, lib, s, img, w, None if fuse_gx else P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, None, Td, Bd, H,
+                              x.device, xin=xin)
             else:
                 _lstm_forward(self, lib, s, img, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device,
                               steps=steps)
