@@ -548,6 +548,18 @@ int lv_log_softmax_rows_f32(const float* in, long ld, int R, int C, const float*
  * w[c] > 0 whose inclusive running sum reaches u[r]*s.  If rounding leaves the running sum short, idx[r] is the last column
  * with positive weight; C - 1 is returned only if no column has positive weight.  A column of probability zero is never drawn. */
 int lv_sample_rows_f32(const float* in, long ld, int R, int C, const float* u, int64_t* idx, void* stream);
+/* the same draw from a tempered, truncated distribution (no counterpart in the reference, whose sample_decode draws from the full
+ * softmax, dec_lstm.py:351-352).  y = in * inv_temp (one f32 multiply); order: larger y first, lower column among equals; Kk = the
+ * first min(top_k, C) columns (top_k == 0: all); w = exp(y - max y); K = the shortest prefix of Kk whose weight reaches
+ * top_p * sum_Kk w (top_p == 1: Kk; never empty).  idx[r] = the first column of K, in COLUMN order, with w > 0 whose inclusive
+ * running sum over K reaches u[r] * sum_K w; the last positive-weight column of K if rounding leaves the sum short; C - 1 only if
+ * no column has positive weight.  Optional outputs (NULL: not written): lp = (x[idx] - max x) - log sum_all exp(x - max x), the
+ * model's log-probability at temperature 1; lq = (y[idx] - max y) - log sum_K w, the log-probability under the distribution drawn
+ * from; kept = |K|, tau = min y over K, ntie = columns of K equal to tau: K is {y > tau} plus the first ntie columns with y == tau.
+ * Rows 16-byte aligned (LV_ERR_ALIGN); inv_temp finite and > 0, top_k >= 0, 0 < top_p <= 1 (LV_ERR_SHAPE).  The result is a
+ * function of the inputs alone: repeated launches give the same bits. */
+int lv_sample_filtered_rows_f32(const float* in, long ld, int R, int C, const float* u, float inv_temp, int top_k, float top_p,
+                                int64_t* idx, float* lp, float* lq, int* kept, float* tau, int* ntie, void* stream);
 
 /* ---- Omniglot path: ResNetEncoderV2 (modules/encoders/enc_resnet_v2.py:27-126) and PixelCNNDecoderV2
  * (modules/decoders/dec_pixelcnn_v2.py:12-195).  Activations NHWC ([N*H*W][C]); a convolution = lv_im2col_f32 +
@@ -724,6 +736,13 @@ int lv_rollout_init_f32(const float* h0, const float* c0, float* h, float* c, in
 int lv_rollout_pick_f32(const float* logits, long ld, const float* u, const float* h_src, const float* c_src, float* h_dst,
                         float* c_dst, int64_t* tok, int* alive, int64_t* ids, int* len, float* score, float* margin,
                         int* counter, int t, int Tmax, int n, int H, int V, int end_tok, void* stream);
+/* the same step with the draw of lv_sample_filtered_rows_f32, bit-equal to it (u [n] mandatory, rows 16-byte aligned): score +=
+ * lp, qscore f32 [n] += lq for a live row; the bookkeeping, the counter gate and the dead-row rules of lv_rollout_pick_f32 (a dead
+ * row keeps qscore as well).  There is no margin. */
+int lv_rollout_pick_filtered_f32(const float* logits, long ld, const float* u, float inv_temp, int top_k, float top_p,
+                                 const float* h_src, const float* c_src, float* h_dst, float* c_dst, int64_t* tok, int* alive,
+                                 int64_t* ids, int* len, float* score, float* qscore, int* counter, int t, int Tmax, int n, int H,
+                                 int V, int end_tok, void* stream);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,7 @@ SIGNATURES = {
     "lv_argmax_rows_f32": [_vp, _l, _i, _i, _vp, _vp],
     "lv_log_softmax_rows_f32": [_vp, _l, _i, _i, _vp, _vp, _l, _vp],
     "lv_sample_rows_f32": [_vp, _l, _i, _i, _vp, _vp, _vp],
+    "lv_sample_filtered_rows_f32": [_vp, _l, _i, _i, _vp, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lv_rng_normal_f32": [_vp, _l, _vp, _u64, _vp],
     "lv_rng_keepmask_u8": [_vp, _l, _f, _vp, _u64, _vp],
     "lv_rng_advance": [_vp, _u64, _vp],
@@ -205,6 +206,8 @@ SIGNATURES = {
     "lv_beam_backtrace": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_rollout_init_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_rollout_pick_f32": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "lv_rollout_pick_filtered_f32": [_vp, _l, _vp, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _i, _i, _i, _i, _i, _i, _vp],
 }
 
 

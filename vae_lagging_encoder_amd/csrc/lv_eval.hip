@@ -220,6 +220,24 @@ __global__ __launch_bounds__(64) void sample_rows_kernel(const float* __restrict
     if (l == 0) idx[r] = pick;
 }
 
+// temperature / top-k / top-p draw (lv_pick.h: lv_block_filtered_pick), one workgroup per row; outputs after idx may be NULL
+__global__ __launch_bounds__(256) void sample_filtered_rows_kernel(const float* __restrict__ in, long ld, int C, const float* __restrict__ u,
+                                                                   float inv_temp, int top_k, float top_p, int64_t* __restrict__ idx,
+                                                                   float* __restrict__ lp, float* __restrict__ lq, int* __restrict__ kept,
+                                                                   float* __restrict__ tau, int* __restrict__ ntie) {
+    __shared__ LvFilteredShared sh;
+    const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const LvFilteredPick p = lv_block_filtered_pick(in + (long)r * ld, C, u[r], inv_temp, top_k, top_p, tid, sh);
+    if (tid == 0) {
+        idx[r] = p.pick;
+        if (lp) lp[r] = p.lp;
+        if (lq) lq[r] = p.lq;
+        if (kept) kept[r] = p.kept;
+        if (tau) tau[r] = p.tau;
+        if (ntie) ntie[r] = p.ntie;
+    }
+}
+
 }  // namespace
 
 // torch.argmax(logits, dim=1) of LSTMDecoder.greedy_decode (dec_lstm.py:304)
@@ -247,6 +265,21 @@ extern "C" int lv_sample_rows_f32(const float* in, long ld, int R, int C, const 
     if (!in || !u || !idx) return LV_ERR_ARG;
     if (R <= 0 || C <= 0 || ld < C) return LV_ERR_SHAPE;
     LV_LAUNCH(sample_rows_kernel, dim3((unsigned)R), dim3(64), 0, stream, in, ld, R, C, u, idx);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// The draw of lv_sample_rows_f32 from a tempered and truncated distribution (the reference has none: dec_lstm.py:351-352 draws from
+// the full softmax).  y = in * inv_temp; K = the top_k largest y (0: all), cut to the shortest prefix that holds top_p of their
+// weight (1: all); idx[r] = the inverse-CDF draw over K in column order with u[r].  The rule in full is lv_pick.h's.
+extern "C" int lv_sample_filtered_rows_f32(const float* in, long ld, int R, int C, const float* u, float inv_temp, int top_k, float top_p,
+                                           int64_t* idx, float* lp, float* lq, int* kept, float* tau, int* ntie, void* stream) {
+    if (!in || !u || !idx) return LV_ERR_ARG;
+    if (R <= 0 || C <= 0 || ld < C) return LV_ERR_SHAPE;
+    if (!(inv_temp > 0.f) || inv_temp == INFINITY || !(top_p > 0.f && top_p <= 1.f) || top_k < 0) return LV_ERR_SHAPE;
+    if ((((uintptr_t)in) & 15) || (ld & 3)) return LV_ERR_ALIGN;
+    LV_LAUNCH(sample_filtered_rows_kernel, dim3((unsigned)R), dim3(256), 0, stream, in, ld, C, u, inv_temp, top_k, top_p, idx, lp, lq, kept,
+              tau, ntie);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

@@ -164,6 +164,28 @@ __global__ __launch_bounds__(64) void rollout_pick_sample_kernel(const float* __
     if (l == 0) rollout_commit(r, pick, (x[pick] - M) - logf(S), tok, alive, ids, len, score, counter, t, Tmax, end_tok);
 }
 
+// filtered sample: lv_sample_filtered_rows_f32's draw (lv_block_filtered_pick), qscore the running log-probability under the
+// distribution drawn from
+__global__ __launch_bounds__(256) void rollout_pick_filtered_kernel(const float* __restrict__ logits, long ld, const float* __restrict__ u,
+                                                                    float inv_temp, int top_k, float top_p, const float* __restrict__ h_src,
+                                                                    const float* __restrict__ c_src, float* __restrict__ h_dst,
+                                                                    float* __restrict__ c_dst, int64_t* __restrict__ tok,
+                                                                    int* __restrict__ alive, int64_t* __restrict__ ids, int* __restrict__ len,
+                                                                    float* __restrict__ score, float* __restrict__ qscore,
+                                                                    int* __restrict__ counter, int t, int Tmax, int H, int V, int end_tok) {
+    __shared__ LvFilteredShared sh;
+    const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (counter[0] <= 0) return;                                    // uniform for the grid (see the note at the top)
+    const int live = alive[r];
+    rollout_move_state<256>(h_src, c_src, h_dst, c_dst, r, H, tid);
+    if (!live) return;                                              // uniform for the workgroup
+    const LvFilteredPick p = lv_block_filtered_pick(logits + (long)r * ld, V, u[r], inv_temp, top_k, top_p, tid, sh);
+    if (tid == 0) {
+        qscore[r] += p.lq;
+        rollout_commit(r, p.pick, p.lp, tok, alive, ids, len, score, counter, t, Tmax, end_tok);
+    }
+}
+
 __global__ __launch_bounds__(256) void rollout_init_kernel(const float* __restrict__ h0, const float* __restrict__ c0, float* __restrict__ h,
                                                            float* __restrict__ c, int64_t* __restrict__ tok, int* __restrict__ alive,
                                                            int* __restrict__ len, float* __restrict__ score, float* __restrict__ margin,
@@ -213,6 +235,25 @@ extern "C" int lv_rollout_pick_f32(const float* logits, long ld, const float* u,
         LV_LAUNCH(rollout_pick_greedy_kernel, dim3((unsigned)n), dim3(256), 0, stream, logits, ld, h_src, c_src, h_dst, c_dst, tok, alive, ids,
                   len, score, margin, counter, t, Tmax, H, V, end_tok);
     }
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// lv_rollout_pick_f32's step with the draw of lv_sample_filtered_rows_f32 (u [n] mandatory; rows 16-byte aligned): the same
+// bookkeeping, counter gate and dead-row rules, and qscore f32 [n] += lq for a live row (a dead row keeps it).  score stays the
+// model's log-probability at temperature 1.
+extern "C" int lv_rollout_pick_filtered_f32(const float* logits, long ld, const float* u, float inv_temp, int top_k, float top_p,
+                                            const float* h_src, const float* c_src, float* h_dst, float* c_dst, int64_t* tok, int* alive,
+                                            int64_t* ids, int* len, float* score, float* qscore, int* counter, int t, int Tmax, int n, int H,
+                                            int V, int end_tok, void* stream) {
+    if (!logits || !u || !h_src || !c_src || !h_dst || !c_dst || !tok || !alive || !ids || !len || !score || !qscore || !counter)
+        return LV_ERR_ARG;
+    if (h_src == h_dst || c_src == c_dst) return LV_ERR_ARG;
+    if (n <= 0 || H <= 0 || V <= 0 || ld < V || Tmax <= 0 || t < 0 || t >= Tmax || end_tok < 0 || end_tok >= V) return LV_ERR_SHAPE;
+    if (!(inv_temp > 0.f) || inv_temp == INFINITY || !(top_p > 0.f && top_p <= 1.f) || top_k < 0) return LV_ERR_SHAPE;
+    if ((((uintptr_t)logits) & 15) || (ld & 3)) return LV_ERR_ALIGN;
+    LV_LAUNCH(rollout_pick_filtered_kernel, dim3((unsigned)n), dim3(256), 0, stream, logits, ld, u, inv_temp, top_k, top_p, h_src, c_src,
+              h_dst, c_dst, tok, alive, ids, len, score, qscore, counter, t, Tmax, H, V, end_tok);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

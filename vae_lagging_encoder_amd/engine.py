@@ -10,8 +10,11 @@ LSTM timestep is a contiguous slab; parameters of one module live in one flat fp
 segments back the module's nn.Parameters, gradients in a parallel flat buffer.
 """
 import ctypes
+import math
+import numbers
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2036,6 +2039,33 @@ def au_accumulate(mu, mean, acc):
 
 
 # ---- generation -------------------------------------------------------------------------------------------
+def sampling_filter(temperature=1.0, top_k=0, top_p=1.0):
+    """The arguments of a tempered / truncated draw as the kernels take them: (inv_temp, top_k, top_p, neutral) with
+    inv_temp = float32(1 / temperature).  `neutral`: the draw is the plain one (temperature 1, no top-k, no top-p).
+    ValueError: temperature not finite or <= 0 (or 1 / temperature not a finite positive float32), top_k not an integer or
+    negative, top_p outside (0, 1]."""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError("temperature must be a positive finite number, got %r" % (temperature,))
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("temperature must be a positive finite number, got %r" % (temperature,))
+    with np.errstate(over="ignore", under="ignore"):
+        inv_temp = float(np.float32(1.0 / t))
+    if not (math.isfinite(inv_temp) and inv_temp > 0.0):
+        raise ValueError("1 / temperature is not a positive finite float32 for temperature %r" % (temperature,))
+    if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or int(top_k) < 0 or int(top_k) > 0x7fffffff:
+        raise ValueError("top_k must be a non-negative integer (0: off), got %r" % (top_k,))
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError("top_p must lie in (0, 1], got %r" % (top_p,))
+    p32 = float(np.float32(p))
+    if not (0.0 < p <= 1.0 and 0.0 < p32 <= 1.0):
+        raise ValueError("top_p must lie in (0, 1], got %r" % (top_p,))
+    return inv_temp, int(top_k), p32, (inv_temp == 1.0 and int(top_k) == 0 and p32 == 1.0)
+
+
 class LSTMDecodeStepper(object):
     """One decoder timestep at a time for greedy / sample / beam decoding (reference modules/decoders/dec_lstm.py:163-367):
     embed(token) ++ z -> LSTM cell -> pred_linear, through the same C-ABI kernels as the training path in exact f32
@@ -2119,6 +2149,20 @@ class LSTMDecodeStepper(object):
         u = u.contiguous().float()
         self.lib.lv_sample_rows_f32(P(logits), logits.stride(0), n, V, P(u), P(idx), stream_ptr(self.device))
         return idx
+
+    def sample_filtered(self, logits, u, temperature=1.0, top_k=0, top_p=1.0):
+        """The draw of `sample` at a temperature, from the top_k most likely words (0: all) cut to the nucleus top_p (1: all):
+        lv_sample_filtered_rows_f32.  -> (idx int64 [n], lp f32 [n]: the model's log-probability of the pick at temperature 1,
+        lq f32 [n]: its log-probability under the distribution drawn from).  Rows of `logits` must be 16-byte aligned."""
+        inv_temp, top_k, top_p, _ = sampling_filter(temperature, top_k, top_p)
+        n, V = logits.shape
+        idx = torch.empty(n, dtype=torch.int64, device=self.device)
+        lp = torch.empty(n, dtype=torch.float32, device=self.device)
+        lq = torch.empty(n, dtype=torch.float32, device=self.device)
+        u = u.contiguous().float()
+        self.lib.lv_sample_filtered_rows_f32(P(logits), logits.stride(0), n, V, P(u), inv_temp, top_k, top_p, P(idx), P(lp), P(lq),
+                                             None, None, None, stream_ptr(self.device))
+        return idx, lp, lq
 
     def log_softmax(self, logits, addrow=None):
         n, V = logits.shape
@@ -2260,9 +2304,14 @@ class LSTMRollout(object):
             self.ws[n] = w
         return w
 
-    def decode(self, z2, start_tok, end_tok, sample=False, generator=None):
+    def decode(self, z2, start_tok, end_tok, sample=False, generator=None, temperature=1.0, top_k=0, top_p=1.0):
         """z2 [n][nz] -> (ids: list of n int lists without <s>, info: dict of numpy arrays score / steps and, for greedy,
-        min_margin, one entry per sentence)."""
+        min_margin, one entry per sentence).  A non-neutral temperature / top_k / top_p (sample only) takes
+        lv_rollout_pick_filtered_f32 as the pick and adds proposal_score, the log-probability of the sentence under the
+        distributions drawn from; score stays the model's log-probability."""
+        inv_temp, top_k, top_p, neutral = sampling_filter(temperature, top_k, top_p)
+        if not neutral and not sample:
+            raise ValueError("temperature / top_k / top_p apply to sampling only")
         st = self.st
         n = z2.shape[0]
         h0, c0 = st.init_state(z2)                                   # refreshes the stepper's view of the parameters
@@ -2277,6 +2326,10 @@ class LSTMRollout(object):
         wih = v["lstm.weight_ih_l0"]
         _gemm(lib, s, 0, 1, n, 4 * H, nz, P(zr), nz, P(wih, ni), ni + nz, P(sw.Zp), 4 * H,
               add1=P(v["lstm.bias_ih_l0"]), ld1=0, mod1=1, add2=P(v["lstm.bias_hh_l0"]), ld2=0, mod2=1)
+        if not neutral:
+            if getattr(w, "qscore", None) is None:
+                w.qscore = torch.empty(n, dtype=torch.float32, device=self.device)
+            w.qscore.zero_()
         poll = max(1, int(self.poll))
         for t in range(T):
             lib.lv_embed_gather_f32(P(v["embed.weight"]), P(w.tok), 1, None, 1.0, P(sw.X), 1, n, ni, V, s)
@@ -2285,18 +2338,26 @@ class LSTMRollout(object):
                                 P(sw.lstm_ws), 1, n, H, s)
             _gemm(lib, s, 0, 1, n, V, H, P(sw.hs, n * H), H, P(v["pred_linear.weight"]), H, P(sw.logits), sw.ldl)
             u = torch.rand(n, device=self.device, generator=generator) if sample else None
-            lib.lv_rollout_pick_f32(P(sw.logits), sw.ldl, P(u), P(sw.hs, n * H), P(sw.cs, n * H), P(sw.hs), P(sw.cs), P(w.tok),
-                                    P(w.alive), P(w.ids), P(w.len), P(w.score), P(w.margin), P(w.counter), t, T, n, H, V,
-                                    end_tok, s)
+            if neutral:
+                lib.lv_rollout_pick_f32(P(sw.logits), sw.ldl, P(u), P(sw.hs, n * H), P(sw.cs, n * H), P(sw.hs), P(sw.cs), P(w.tok),
+                                        P(w.alive), P(w.ids), P(w.len), P(w.score), P(w.margin), P(w.counter), t, T, n, H, V,
+                                        end_tok, s)
+            else:
+                lib.lv_rollout_pick_filtered_f32(P(sw.logits), sw.ldl, P(u), inv_temp, top_k, top_p, P(sw.hs, n * H), P(sw.cs, n * H),
+                                                 P(sw.hs), P(sw.cs), P(w.tok), P(w.alive), P(w.ids), P(w.len), P(w.score),
+                                                 P(w.qscore), P(w.counter), t, T, n, H, V, end_tok, s)
             if (t + 1) % poll == 0 and t + 1 < T and int(w.counter.item()) == 0:      # the only host read of the loop
                 break
-        # one device-to-host copy: ids | len | the bits of (score, min margin)
+        # one device-to-host copy: ids | len | the bits of (score, min margin[, proposal score])
+        fcols = (w.score, w.margin) if neutral else (w.score, w.margin, w.qscore)
         out = torch.cat((w.ids, w.len.to(torch.int64).unsqueeze(1),
-                         torch.stack((w.score, w.margin), dim=1).view(torch.int32).to(torch.int64)), dim=1).cpu()
+                         torch.stack(fcols, dim=1).view(torch.int32).to(torch.int64)), dim=1).cpu()
         lens = out[:, T].tolist()
         ids = [row[:m] for row, m in zip(out[:, :T].tolist(), lens)]
         fl = out[:, T + 1:].to(torch.int32).contiguous().view(torch.float32).numpy()
         info = {"score": fl[:, 0].copy(), "steps": out[:, T].numpy().copy()}
         if not sample:
             info["min_margin"] = fl[:, 1].copy()
+        if not neutral:
+            info["proposal_score"] = fl[:, 2].copy()
         return ids, info

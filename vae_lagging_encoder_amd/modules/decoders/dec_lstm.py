@@ -229,14 +229,16 @@ class LSTMDecoder(DecoderBase):
         ro.poll = self.rollout_poll
         return ro
 
-    def _decode_loop(self, z, pick, sample, generator, return_info):
+    def _decode_loop(self, z, pick, sample, generator, return_info, filt=None):
         batch_size = z.size(0)
         if self.batched_rollout and batch_size > 0:
             with torch.no_grad():
                 ids, info = self._rollout(z.device).decode(z.reshape(batch_size, -1).float(), self.vocab["<s>"], self.vocab["</s>"],
-                                                            sample=sample, generator=generator)
+                                                            sample=sample, generator=generator, **(filt or {}))
             decoded = [[self.vocab.id2word(w) for w in row] for row in ids]
             return (decoded, info) if return_info else decoded
+        if filt:
+            return self._roll_out_filtered(z, generator, return_info, filt)
         if not return_info:
             return self._roll_out(z, pick)
         # the per-step route with the same per-sentence quantities, from the stepper's helpers
@@ -259,6 +261,29 @@ class LSTMDecoder(DecoderBase):
             info["min_margin"] = torch.where(live, gap, torch.full_like(gap, float("inf"))).min(dim=1)[0].numpy().astype(np.float32)
         return decoded, info
 
+    def _roll_out_filtered(self, z, generator, return_info, filt):
+        """The per-step route of a tempered / truncated sample_decode: the loop of _roll_out with lv_sample_filtered_rows_f32 as the
+        pick.  The running sums are kept the way the device route keeps them (f32, one addition per live step), so both routes
+        return the same bits."""
+        n, dev = z.size(0), z.device
+        end = self.vocab["</s>"]
+        run = {"score": torch.zeros(n, dtype=torch.float32, device=dev), "q": torch.zeros(n, dtype=torch.float32, device=dev),
+               "alive": torch.ones(n, dtype=torch.bool, device=dev)}
+
+        def pick(st, logits):
+            u = torch.rand(logits.shape[0], device=logits.device, generator=generator)
+            tok, lp, lq = st.sample_filtered(logits, u, **filt)
+            live = run["alive"]
+            run["score"] = torch.where(live, run["score"] + lp, run["score"])
+            run["q"] = torch.where(live, run["q"] + lq, run["q"])
+            run["alive"] = live & (tok != end)
+            return tok
+        decoded = self._roll_out(z, pick)
+        if not return_info:
+            return decoded
+        return decoded, {"score": run["score"].cpu().numpy(), "steps": np.asarray([len(s) for s in decoded], dtype=np.int64),
+                         "proposal_score": run["q"].cpu().numpy()}
+
     def greedy_decode(self, z, return_info=False):
         """Greedy decoding from z (batch_size, nz) -> list of word lists (reference dec_lstm.py:270-318): no <s>, </s> included
         when emitted, at most 99 words.  return_info=True also returns a dict of per-sentence numpy arrays: `score`
@@ -266,16 +291,27 @@ class LSTMDecoder(DecoderBase):
         steps)."""
         return self._decode_loop(z, lambda st, logits: st.argmax(logits), False, None, return_info)
 
-    def sample_decode(self, z, generator=None, return_info=False):
+    def sample_decode(self, z, generator=None, return_info=False, temperature=1.0, top_k=0, top_p=1.0):
         """Ancestral sampling from z (reference dec_lstm.py:320-367).  The categorical draw is an inverse-CDF pick from a device
         uniform (torch.rand, one call of batch_size values per step; `generator` makes it reproducible) instead of
         torch.multinomial's sampler: same distribution, different stream.  Both routes draw the same uniforms in the same order;
         the device route consumes up to rollout_poll - 1 further draws after the last sentence has ended.  return_info=True also
-        returns `score` and `steps` per sentence."""
+        returns `score` and `steps` per sentence.
+
+        temperature / top_k / top_p (the reference has none) draw every word from softmax(logits / temperature) restricted to the
+        top_k most likely words (0: all) and then to the shortest prefix of those that holds top_p of their probability (1: all),
+        renormalised: lv_pick.h's rule, lv_rollout_pick_filtered_f32 on the device route and lv_sample_filtered_rows_f32 on the
+        per-step route, from the same uniforms.  `score` stays log p(words | z) under the model itself; return_info=True then
+        adds `proposal_score`, the log-probability of the sentence under the distributions actually drawn from.  With the
+        neutral values (1.0, 0, 1.0) the call is the plain one, launch for launch.  ValueError before any launch: temperature
+        <= 0 or not finite, top_k not an integer or negative, top_p outside (0, 1]."""
+        neutral = _eng.sampling_filter(temperature, top_k, top_p)[3]
+        filt = None if neutral else {"temperature": temperature, "top_k": top_k, "top_p": top_p}
+
         def pick(st, logits):
             u = torch.rand(logits.shape[0], device=logits.device, generator=generator)
             return st.sample(logits, u)
-        return self._decode_loop(z, pick, True, generator, return_info)
+        return self._decode_loop(z, pick, True, generator, return_info, filt)
 
     # True: beam_search_decode decodes the whole batch together through engine.LSTMBeamSearcher (lv_beam.hip) when the shape is
     # inside its envelope; False forces the sentence-by-sentence route below (A/B runs, tests)

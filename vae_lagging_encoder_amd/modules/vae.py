@@ -109,18 +109,28 @@ class VAE(nn.Module):
         return self.encode(x, 1)[1]
 
     # ---- generation (delegated; generation itself is outside the hot path) -----------------------------
-    def decode(self, z, strategy, K=5, return_info=False):
+    def decode(self, z, strategy, K=5, return_info=False, temperature=1.0, top_k=0, top_p=1.0):
         """return_info: also the per-sentence dict the decoder's beam_search_decode / greedy_decode / sample_decode returns with
-        return_info=True."""
+        return_info=True.  temperature / top_k / top_p: sample_decode's; non-neutral values with another strategy raise
+        ValueError."""
         if strategy not in _GENERATORS:
             raise ValueError("the decoding strategy is not supported")
+        neutral = _eng.sampling_filter(temperature, top_k, top_p)[3]
+        if not neutral and strategy != "sample":
+            raise ValueError("temperature / top_k / top_p apply to the decoding strategy \"sample\" only")
         fn = getattr(self.decoder, _GENERATORS[strategy])
         if strategy == "beam":
             return fn(z, K, return_info=True) if return_info else fn(z, K)
+        if not neutral:
+            return fn(z, return_info=return_info, temperature=temperature, top_k=top_k, top_p=top_p)
         return fn(z, return_info=True) if return_info else fn(z)
 
-    def reconstruct(self, x, decoding_strategy="greedy", K=5):
-        return self.decode(self.sample_from_inference(x).squeeze(1), decoding_strategy, K)
+    def reconstruct(self, x, decoding_strategy="greedy", K=5, temperature=1.0, top_k=0, top_p=1.0):
+        neutral = _eng.sampling_filter(temperature, top_k, top_p)[3]
+        if not neutral and decoding_strategy != "sample":
+            raise ValueError("temperature / top_k / top_p apply to the decoding strategy \"sample\" only")
+        return self.decode(self.sample_from_inference(x).squeeze(1), decoding_strategy, K, temperature=temperature, top_k=top_k,
+                           top_p=top_p)
 
     def sample_from_prior(self, nsamples):
         return self.prior.sample((nsamples,))
