@@ -362,6 +362,25 @@ int lv_loss_assemble_ns_rng_f32(const float* nll, const float* kl, const float* 
                                 float* loss, float* rec, float* rowscale, float* dkl, float* acc_dev, int T, int B, int ns,
                                 uint64_t* rng_state, uint64_t rng_inc, void* stream);
 
+/* ---- training on the importance-weighted bound, objective "iw" (lv_iw.hip): loss_b = -(logsumexp_s log w_s - log ns),
+ * log w_s = -rec_s - w*(sum_j z_sj^2 / 2 - sum_j eps_sj^2 / 2 - sum_j logvar_j / 2) (log q in its eps form, exact for
+ * z = mu + eps*sigma; w = kl_weight_dev[0]; w = 1 is VAE.nll_iw(x, ns, ns), vae.py:100-129), wn = softmax_s(log w), max-subtracted:
+ * a weight may underflow to exactly 0.  nll [T][B*ns] (T = 1: nll holds rec_s itself); mulv [B][2nz]; eps, z [B][ns][nz];
+ * rec[b] = (1/ns) sum_s rec_s; rowscale[b*ns + s] = g_loss[b]*wn_s (seed of the decoder backward); wz[b][s] = w*rowscale[b*ns + s];
+ * logw [B][ns] may be NULL; acc_dev[0..2] += sum_b (loss, rec, kl) with kl [B] the analytic KL, reported only.  Any ns >= 1;
+ * ns = 1 gives wn = 1 and rowscale = g_loss bit for bit. */
+int lv_loss_assemble_iw_f32(const float* nll, const float* mulv, const float* eps, const float* z, const float* kl,
+                            const float* kl_weight_dev, const float* g_loss, float* loss, float* rec, float* rowscale,
+                            float* wz, float* logw, float* acc_dev, int T, int B, int ns, int nz, void* stream);
+/* the same + rng_state[1] += rng_inc, as lv_loss_assemble_ns_rng_f32 */
+int lv_loss_assemble_iw_rng_f32(const float* nll, const float* mulv, const float* eps, const float* z, const float* kl,
+                                const float* kl_weight_dev, const float* g_loss, float* loss, float* rec, float* rowscale,
+                                float* wz, float* logw, float* acc_dev, int T, int B, int ns, int nz, uint64_t* rng_state,
+                                uint64_t rng_inc, void* stream);
+/* the weights' direct gradient for the autograd route (dz itself travels through lv_reparam_kl_bwd_f32): dmulv [B][2nz] ('='),
+ * dmu_j = sum_s c_s z_sj, dlogvar_j = sum_s c_s z_sj eps_sj sigma_j / 2 - sum_s c_s / 2, c = wz [B][ns] */
+int lv_reparam_iw_bwd_f32(const float* mulv, const float* eps, const float* wz, float* dmulv, int B, int ns, int nz, void* stream);
+
 /* ---- the batch-sized ends of the two LSTM networks, one launch each (lv_head.hip) --------------------------------------
  * LSTMEncoder's head + GaussianEncoderBase.encode (enc_lstm.py:62-64, encoder.py:40-57): mulv = hT . W_lin^T,
  * z = mu + eps*exp(logvar/2), kl = 0.5*sum(mu^2 + exp(logvar) - logvar - 1).  hT [B][H], W_lin [2nz][H], eps/z [B][ns][nz] */
@@ -372,6 +391,12 @@ int lv_enc_head_fwd_f32(const float* hT, const float* w_lin, const float* eps, f
 int lv_enc_head_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* dkl,
                         const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin, int B, int H, int ns,
                         int nz, void* stream);
+/* the same for the importance-weighted objective: wz [B][ns] (c_s of lv_loss_assemble_iw_f32) in place of dkl;
+ * t_sj = dz_sj + c_s z_sj, dmu_j = sum_s t_sj, dlogvar_j = sum_s t_sj eps_sj sigma_j / 2 - sum_s c_s / 2.  With wz all zeros the
+ * three outputs are bit-identical to lv_enc_head_bwd_f32 with dkl all zeros. */
+int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz,
+                           const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin, int B, int H, int ns,
+                           int nz, void* stream);
 /* LSTMDecoder.decode's z-dependent prologue (dec_lstm.py:95-101): c0 = z W_trans^T, h0 = tanh(c0) (G7) and
  * Zp = z W_ih[:, col0:col0+nz]^T + b_ih + b_hh, the contribution of cat((word_embed, z_), -1) to the input projection;
  * Zp gate-major [B][4H], or with column 4u+g (unit_major != 0) for the unit-major Gx epilogue */

@@ -58,6 +58,10 @@ SIGNATURES = {
     "lv_repeat_rows_i64": [_vp, _vp, _i, _i, _i, _vp],
     "lv_loss_assemble_ns_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_loss_assemble_ns_rng_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _u64, _vp],
+    "lv_loss_assemble_iw_f32": [_vp] * 13 + [_i, _i, _i, _i, _vp],
+    "lv_loss_assemble_iw_rng_f32": [_vp] * 13 + [_i, _i, _i, _i, _vp, _u64, _vp],
+    "lv_reparam_iw_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_enc_head_iw_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_enc_head_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_enc_head_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_dec_tail_parts": [_i],

@@ -101,7 +101,10 @@ __global__ __launch_bounds__(256) void enc_head_fwd_kernel(const float* __restri
 // and the h_T columns [B][64] -- is staged in LDS with fully parallel loads first; the dot products then run out of LDS
 // (a thread that walks a runtime-length loop of global load -> fma pairs pays one memory round trip per iteration: the
 // first versions of these kernels took 60-250 us that way).  dz may arrive as `parts` partial sums [parts][B][ns][nz].
-template <int HB_COLS>
+// IW (objective "iw", lv_iw.hip): `dkl` is wz [B][ns], c_s = beta * g * wn_s, and the analytic-KL terms give way to the per-sample
+// ones: t_sj = dz_sj + c_s z_sj, dmu_j = sum_s t_sj, dlogvar_j = sum_s t_sj 1/2 eps_sj sigma_j - 1/2 sum_s c_s.  With wz all zeros
+// every operation reduces to the one the plain kernel does with dkl all zeros: the same bits.
+template <int HB_COLS, bool IW>
 __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restrict__ mulv, const float* __restrict__ eps,
                                                            const float* __restrict__ dz, int parts, const float* __restrict__ dkl,
                                                            const float* __restrict__ hT, const float* __restrict__ wlin,
@@ -171,15 +174,30 @@ __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restri
         const int bb = i / nz, j = i % nz;
         const float m = mulv[(long)bb * nz2 + j], lv = mulv[(long)bb * nz2 + nz + j];
         const float sdv = expf(0.5f * lv);
-        float gz = 0.f, gze = 0.f;
-        for (int s = 0; s < ns; ++s) {
-            const long zi = ((long)bb * ns + s) * nz + j;
-            const float g = sg[zi];
-            gz += g;
-            gze += g * eps[zi];
+        float gz = 0.f, gze = 0.f, dm, dl;
+        if (IW) {
+            float sc = 0.f;
+            for (int s = 0; s < ns; ++s) {
+                const long zi = ((long)bb * ns + s) * nz + j;
+                const float e = eps[zi], c = dkl[(long)bb * ns + s];
+                const float g = sg[zi] + c * (m + e * sdv);
+                gz += g;
+                gze += g * e;
+                sc += c;
+            }
+            dm = gz;
+            dl = gze * (0.5f * sdv) - 0.5f * sc;
+        } else {
+            for (int s = 0; s < ns; ++s) {
+                const long zi = ((long)bb * ns + s) * nz + j;
+                const float g = sg[zi];
+                gz += g;
+                gze += g * eps[zi];
+            }
+            const float gk = dkl[bb];
+            dm = gz + gk * m;
+            dl = gze * (0.5f * sdv) + gk * (0.5f * (expf(lv) - 1.f));
         }
-        const float gk = dkl[bb];
-        const float dm = gz + gk * m, dl = gze * (0.5f * sdv) + gk * (0.5f * (expf(lv) - 1.f));
         sd[bb * nz2 + j] = dm;
         sd[bb * nz2 + nz + j] = dl;
         if (blockIdx.x == 0) { dmulv[(long)bb * nz2 + j] = dm; dmulv[(long)bb * nz2 + nz + j] = dl; }
@@ -326,8 +344,26 @@ extern "C" int lv_enc_head_bwd_f32(const float* mulv, const float* eps, const fl
     if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
     const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
     if ((base + per_col * 16) * sizeof(float) <= 64000)
-        LV_LAUNCH(enc_head_bwd_kernel<16>, dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
+        LV_LAUNCH((enc_head_bwd_kernel<16, false>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
                   mulv, eps, dz, dz_parts, dkl, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz);
+    else
+        return LV_ERR_UNSUPPORTED;
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// The same for the importance-weighted objective (lv_iw.hip): wz [B][ns] = c_s from lv_loss_assemble_iw_f32 in place of dkl;
+// dz [dz_parts][B][ns][nz] already carries g * wn_s through the decoder backward's rowscale.  With wz all zeros dmulv, dhT and
+// gW_lin are bit-identical to lv_enc_head_bwd_f32 with dkl all zeros.
+extern "C" int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz,
+                                      const float* hT, const float* wlin, float* dmulv, float* dhT, float* gwlin, int B, int H,
+                                      int ns, int nz, void* stream) {
+    if (!mulv || !eps || !dz || !wz || !hT || !wlin || !dmulv || !dhT || !gwlin) return LV_ERR_ARG;
+    if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
+    const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
+    if ((base + per_col * 16) * sizeof(float) <= 64000)
+        LV_LAUNCH((enc_head_bwd_kernel<16, true>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
+                  mulv, eps, dz, dz_parts, wz, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz);
     else
         return LV_ERR_UNSUPPORTED;
     LV_CHECK_LAUNCH();

@@ -1302,7 +1302,9 @@ class LSTMEncoderEngine(object):
         been queued; the LSTM weight-gradient GEMMs follow it (data parallel: that bucket's all-reduce runs under them).
 
         head = (eps, dz [parts][B][ns][nz], parts, dkl [B]) instead of dmulv: the backward of reparameterise + KL runs in
-        the head's launch (fused driver; dmulv is then produced into the workspace)."""
+        the head's launch (fused driver; dmulv is then produced into the workspace).  A fifth element "iw" selects the
+        importance-weighted objective's head backward (lv_enc_head_iw_bwd_f32): the fourth is then wz [B][ns], the per-sample
+        seeds of lv_loss_assemble_iw_f32, in place of the analytic-KL seed."""
         x, B, T, g = self.last
         if gen is not None and gen != g:
             raise _lib.LvaeError("encoder activations were overwritten by a later forward(); the HIP engine keeps "
@@ -1313,6 +1315,12 @@ class LSTMEncoderEngine(object):
         V, ni, H, nz2 = self.dims()
         w = self._ws(B, T)
         v, gv = f.views, f.gviews
+        iw = head is not None and len(head) == 5 and head[4] == "iw"
+        if head is not None:
+            head = head[:4]
+        if iw and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
+            raise _lib.LvaeError("objective 'iw' runs on the one-launch encoder head (lv_enc_head_iw_bwd_f32); B = %d, nsamples = %d, "
+                                 "nz = %d is beyond its LDS budget" % (B, head[0].shape[1], nz2 // 2))
         if head is not None and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
             eps, dz, parts, dkl = head
             assert parts == 1
@@ -1321,8 +1329,9 @@ class LSTMEncoderEngine(object):
             _gemm(lib, s, 1, 0, nz2, H, B, P(w.dmulv), nz2, P(w.hs, T * B * H), H, P(gv["linear.weight"]), H)
         elif head is not None:
             eps, dz, parts, dkl = head
-            lib.lv_enc_head_bwd_f32(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(w.hs, T * B * H), P(v["linear.weight"]), P(w.dmulv),
-                                    P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
+            head_bwd = lib.lv_enc_head_iw_bwd_f32 if iw else lib.lv_enc_head_bwd_f32
+            head_bwd(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(w.hs, T * B * H), P(v["linear.weight"]), P(w.dmulv),
+                     P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
         else:
             dmulv = dmulv.contiguous()
             # head: dh_T = dmulv . W_lin ; dW_lin = dmulv^T . h_T
@@ -1944,6 +1953,33 @@ def reparam_kl_backward(mulv, eps, dz, dkl):
     # (contiguous copies are held in locals until the launch is queued: a temporary's block may be handed out again at once)
     mulv_c, eps_c, dz_c, dkl_c = mulv.contiguous(), eps.contiguous(), dz.contiguous(), dkl.contiguous()
     lib.lv_reparam_kl_bwd_f32(P(mulv_c), P(eps_c), P(dz_c), P(dkl_c), P(dmulv), B, ns, nz, s)
+    return dmulv
+
+
+def iw_assemble(rec_s, mulv, eps, z, kl, klw, g_loss, want_logw=False):
+    """Loss assembly of the importance-weighted objective on per-sample reconstruction errors (lv_loss_assemble_iw_f32 with T = 1):
+    rec_s [B][ns], mulv [B][2nz], eps / z [B][ns][nz], kl / g_loss [B], klw: device float[1] -> loss [B], rec [B] (mean over the
+    samples), rowscale [B][ns] = g_loss * softmax_s(log w), wz [B][ns] = klw * rowscale, logw [B][ns] or None."""
+    lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
+    B, ns, nz = eps.shape
+    f32 = dict(dtype=torch.float32, device=mulv.device)
+    t = [a.contiguous() for a in (rec_s, mulv, eps, z, kl, klw, g_loss)]      # held until the launch is queued
+    loss, rec = torch.empty(B, **f32), torch.empty(B, **f32)
+    rowscale, wz = torch.empty(B, ns, **f32), torch.empty(B, ns, **f32)
+    logw = torch.empty(B, ns, **f32) if want_logw else None
+    acc = torch.zeros(3, **f32)
+    lib.lv_loss_assemble_iw_f32(*[P(a) for a in t], P(loss), P(rec), P(rowscale), P(wz), P(logw) if want_logw else None, P(acc),
+                                1, B, ns, nz, s)
+    return loss, rec, rowscale, wz, logw
+
+
+def reparam_iw_backward(mulv, eps, wz):
+    """The weights' direct gradient to [mu | logvar] (lv_reparam_iw_bwd_f32); wz [B][ns] from iw_assemble."""
+    lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
+    B, ns, nz = eps.shape
+    dmulv = torch.empty_like(mulv)
+    mulv_c, eps_c, wz_c = mulv.contiguous(), eps.contiguous(), wz.contiguous()
+    lib.lv_reparam_iw_bwd_f32(P(mulv_c), P(eps_c), P(wz_c), P(dmulv), B, ns, nz, s)
     return dmulv
 
 

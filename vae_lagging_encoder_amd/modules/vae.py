@@ -16,6 +16,27 @@ from .utils import log_sum_exp
 _GENERATORS = {"beam": "beam_search_decode", "greedy": "greedy_decode", "sample": "sample_decode"}
 
 
+class _IWBoundFn(torch.autograd.Function):
+    """(rec_s [B][ns], mulv) -> (loss [B], rec [B]) of the importance-weighted bound (lv_loss_assemble_iw_f32 on T = 1).  z enters as
+    data: its gradient through the decoder arrives with rec_s (seeded with g * softmax_s(log w)), the weights' direct dependence on
+    z = mu + eps * sigma and on logvar goes straight to mulv (lv_reparam_iw_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, rec_s, mulv, eps, z, kl, klw):
+        one = torch.ones(mulv.shape[0], dtype=torch.float32, device=mulv.device)
+        loss, rec, _, _, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, one)
+        ctx.save_for_backward(rec_s, mulv, eps, z, kl, klw)
+        ctx.mark_non_differentiable(rec)
+        return loss, rec
+
+    @staticmethod
+    def backward(ctx, dloss, drec):
+        rec_s, mulv, eps, z, kl, klw = ctx.saved_tensors
+        # the same launch with the incoming gradient as seed: rowscale = dloss * wn, wz = kl_weight * rowscale
+        _, _, rowscale, wz, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, dloss)
+        return rowscale, _eng.reparam_iw_backward(mulv, eps, wz), None, None, None, None
+
+
 class VAE(nn.Module):
     """Encoder q(z|x), decoder p(x|z), prior N(0, I)."""
 
@@ -104,6 +125,25 @@ class VAE(nn.Module):
         dec_extra = {} if masks is None else {"masks": masks}
         rec = self.decoder.reconstruct_error(x, z, **dec_extra).mean(dim=1)
         return rec + kl_weight * kl, rec, kl
+
+    def loss_iw(self, x, kl_weight=1.0, nsamples=1, noise=None):
+        """The importance-weighted bound as a training objective -> (loss, rec, KL), each (batch,):
+        loss = -(logsumexp_s log w_s - log nsamples), log w_s = log p(x|z_s) + kl_weight * (log p(z_s) - log q(z_s|x)) -- with
+        kl_weight = 1 what nll_iw(x, nsamples, nsamples) estimates (reference vae.py:100-129) -- differentiable through the
+        reparameterised samples; rec is the sample mean of the reconstruction error and KL the analytic one, both for reports only
+        (detached).  nsamples = 1 is a single-sample Monte-Carlo ELBO: its KL term is the sampled log q - log p, not the analytic KL.
+        Works with every decoder that has reconstruct_error(x, z) -> (batch, nsamples).  noise: as `loss`."""
+        from .encoders.encoder import _ReparamKLFn
+        eps, masks = (None, None) if noise is None else (noise[0], (noise[1], noise[2]))
+        x = self._batch(x)
+        mulv = self.encoder._forward_mulv(x)
+        eps = self.encoder._draw_eps(mulv.shape[0], nsamples, mulv.shape[1] // 2, mulv.device, eps)
+        z, kl = _ReparamKLFn.apply(mulv, eps)
+        dec_extra = {} if masks is None else {"masks": masks}
+        rec_s = self.decoder.reconstruct_error(x, z, **dec_extra)
+        klw = torch.full((1,), float(kl_weight), dtype=torch.float32, device=mulv.device)
+        loss, rec = _IWBoundFn.apply(rec_s, mulv, eps, z.detach(), kl.detach(), klw)
+        return loss, rec, kl.detach()
 
     def KL(self, x):
         return self.encode(x, 1)[1]

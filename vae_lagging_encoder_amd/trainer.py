@@ -73,8 +73,15 @@ class AggressiveTextTrainer(object):
 
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
                  precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0):
-        """nsamples = ns > 1: text.py --nsamples, VAE.loss(x, kl_weight, nsamples=ns) (vae.py:79-98) -- ns reparameterised samples per
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0, objective="elbo"):
+        """objective = "elbo" (default: rec averaged over the samples + kl_weight * analytic KL, VAE.loss) or "iw": the step minimises
+        the importance-weighted bound -(logsumexp_s log w_s - log ns) that VAE.nll_iw(x, ns, ns) estimates (vae.py:100-129; kl_weight
+        scales log q - log p inside log w, 1 is the reference's), differentiated through the reparameterised samples: the decoder rows
+        are seeded with g * softmax_s(log w) instead of g / ns and the encoder head takes per-sample terms instead of the analytic-KL
+        gradient (lv_loss_assemble_iw_f32, lv_enc_head_iw_bwd_f32).  loss_sum reports the bound, rec_sum the sample
+        mean of rec, kl_sum the analytic KL.  "iw" always runs the multi-sample route and shares its fences, also with nsamples = 1 --
+        a single-sample Monte-Carlo ELBO whose KL term is the sampled log q - log p, NOT the analytic KL.  st.logw [B][ns] holds log w.
+        nsamples = ns > 1: text.py --nsamples, VAE.loss(x, kl_weight, nsamples=ns) (vae.py:79-98) -- ns reparameterised samples per
         sentence, the decoder on B * ns rows (row b * ns + s), the reconstruction term averaged over the samples; the report sums stay
         sums over the B sentences.  Noise shapes: eps [B][ns][nz], mask_in [B][T-1][ni] (dropout_in acts before the expansion: one mask
         per sentence), mask_out [B*ns][T-1][H].  The word half of the decoder's input projection and its backward run once per
@@ -124,12 +131,16 @@ class AggressiveTextTrainer(object):
         self.nsamples = int(nsamples)
         if self.nsamples < 1:
             raise ValueError("nsamples must be >= 1, not %r" % (nsamples,))
-        if self.nsamples > 1:
+        if objective not in ("elbo", "iw"):
+            raise ValueError("objective: 'elbo' or 'iw', not %r" % (objective,))
+        self.objective = objective
+        if self.nsamples > 1 or objective == "iw":
             fenced = [n for n, on in (("grad_sync", grad_sync is not None), ("use_graph=True", bool(use_graph)),
                                       ("micro_batches > 1", self.micro_batches > 1), ("decoder_grads='norm'", decoder_grads == "norm")) if on]
             if fenced:
-                raise ValueError("nsamples = %d runs on a single GPU in eager mode with micro_batches = 1 and decoder_grads = 'full'; "
-                                 "not implemented together with: %s" % (self.nsamples, ", ".join(fenced)))
+                raise ValueError("nsamples = %d%s runs on a single GPU in eager mode with micro_batches = 1 and decoder_grads = 'full'; "
+                                 "not implemented together with: %s" % (self.nsamples, " with objective = 'iw'" if objective == "iw" else "",
+                                                                       ", ".join(fenced)))
         self.fold_norm = bool(fold_norm)
         assert decoder_grads in ("full", "norm")
         self.decoder_grads = decoder_grads
@@ -377,6 +388,9 @@ class AggressiveTextTrainer(object):
             st.gl = torch.full((B,), 1.0 / (B * parts), dtype=torch.float32, device=d)   # d(mean_b loss_b)/d loss_b
             st.rowscale = torch.empty(B * ns, dtype=torch.float32, device=d)
             st.dkl = torch.empty(B, dtype=torch.float32, device=d)
+            if self.objective == "iw":
+                st.wz = torch.empty(B, ns, dtype=torch.float32, device=d)                # beta * g * softmax_s(log w): the head's seeds
+                st.logw = torch.empty(B, ns, dtype=torch.float32, device=d)
             st.dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
             st.graphs = {}
             st.x_key = None
@@ -417,7 +431,15 @@ class AggressiveTextTrainer(object):
         w = self.dec._ws(B * ns, T - 1, ns)
         # rec, loss, the running report sums and the seeds of mean_b(loss_b).backward(), one launch
         # (report sums into the pending slots: committed by the transaction gate; the Philox offset moves on here when drawn)
-        if ns > 1 and draw:
+        iw = self.objective == "iw"
+        if iw:
+            a = (P(w.nll), P(mulv), P(st.eps), P(st.z), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec),
+                 P(st.rowscale), P(st.wz), P(st.logw), self._s(10), T - 1, B, ns, st.eps.shape[2])
+            if draw:
+                lib.lv_loss_assemble_iw_rng_f32(*a, P(self.rng_state), 1, s)
+            else:
+                lib.lv_loss_assemble_iw_f32(*a, s)
+        elif ns > 1 and draw:
             lib.lv_loss_assemble_ns_rng_f32(P(w.nll), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
                                             self._s(10), T - 1, B, ns, P(self.rng_state), 1, s)
         elif ns > 1:
@@ -460,7 +482,8 @@ class AggressiveTextTrainer(object):
                 hook = start
             else:
                 start()                   # step kernels: the collective runs under the whole encoder backward
-        self.enc.backward(None, head=(st.eps, dzp, parts, st.dkl), after_bptt=hook, after_embed=bucket)
+        head = (st.eps, dzp, parts, st.wz, "iw") if iw else (st.eps, dzp, parts, st.dkl)
+        self.enc.backward(None, head=head, after_bptt=hook, after_embed=bucket)
         self.dec.join()           # decoder weight-gradient GEMMs ran on the side stream underneath the BPTT chains
         if self.grad_sync is not None and self.grad_sync.active:
             # data parallel: this rank's timeout flag rides in the tail padding of the encoder gradient (exchanged by sync())
@@ -622,7 +645,7 @@ class AggressiveTextTrainer(object):
         steps): should a persistent recurrence of it time out, the device voids it -- and everything queued behind it -- and the
         read replays the voided steps one rung down the fallback ladder (_settle).  x (and injected noise) must therefore stay
         unmodified until then, as they must for the sorted-token cache."""
-        if self.nsamples > 1 and noise is not None:
+        if (self.nsamples > 1 or self.objective == "iw") and noise is not None:
             self._check_noise(x, noise)
         self._queue_step(x, kl_weight, noise, update)
         self._journal.append((x, float(kl_weight), noise, update))

@@ -50,9 +50,22 @@ def guarded_eval(vae, fn, log=print):
     raise _eng._lib.LvaeError("an evaluation pass kept reporting persistent-launch timeouts on every rung of the fallback ladder")
 
 
+def _objective(args, trainer):
+    """args.objective ("elbo" when the attribute is missing; "iw": the training steps minimise the importance-weighted bound,
+    AggressiveTextTrainer(objective="iw")); a trainer that is handed in must have been built with the same one.  The evaluation
+    passes are the same for both."""
+    objective = getattr(args, "objective", "elbo")
+    if objective not in ("elbo", "iw"):
+        raise ValueError("args.objective: 'elbo' or 'iw', not %r" % (objective,))
+    if trainer is not None and getattr(trainer, "objective", "elbo") != objective:
+        raise ValueError("args.objective = %r, but the trainer was built with objective = %r" % (objective, getattr(trainer, "objective", "elbo")))
+    return objective
+
+
 class TextTrainingLoop(object):
     """args fields read (text.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
-    iw_nsamples, momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...))."""
+    iw_nsamples, momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...)), and
+    objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...))."""
 
     def __init__(self, vae, train_batches, val_batches, test_batches, args, n_train_sentences=None, trainer=None,
                  log=print, np_rng=None, seed=783435, noise_fn=None, epoch_hook=None):
@@ -72,8 +85,10 @@ class TextTrainingLoop(object):
         self.nsamples = int(getattr(args, "nsamples", 1))
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
+        self.objective = _objective(args, trainer)
         self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
-                                                                                 nsamples=self.nsamples, momentum=self.momentum)
+                                                                                 nsamples=self.nsamples, momentum=self.momentum,
+                                                                                 objective=self.objective)
         if hasattr(self.trainer, "prepare_batches"):
             self.trainer.prepare_batches(train_batches)          # per-batch index structures, built once with the batch list
         self.rng = np_rng if np_rng is not None else np.random
@@ -370,7 +385,8 @@ class ToyTrainingLoop(object):
       * at the end the best checkpoint is reloaded and the importance-weighted NLL is computed on `iw_batches` (toy.py uses the
         test set in batches of one sentence).
     args fields read (toy.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
-    iw_nsamples, optim, plot_mode, num_plot, plot_niter, zmin, zmax, dz.
+    iw_nsamples, optim, plot_mode, num_plot, plot_niter, zmin, zmax, dz, objective ("elbo" when missing, or "iw": the
+    single-sample importance-weighted step, AggressiveTextTrainer(objective="iw")).
 
     plot_data: the (batch, lengths) pair MonoTextData.data_sample returns (toy.py:304), or the batch tensor alone.
     noise_fn / epoch_hook / np_rng: as TextTrainingLoop's.  plot_dir: when given, every plot is also written as toy.py writes it
@@ -398,8 +414,9 @@ class ToyTrainingLoop(object):
         self.plot_x = plot_data[0] if isinstance(plot_data, (tuple, list)) else plot_data
         self.single = args.plot_mode == "single"
         self.opt = {"not_improved": 0, "lr": self.LR0[self.optim], "best_loss": 1e4}
+        self.objective = _objective(args, trainer)
         if trainer is None:
-            trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim)
+            trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim, objective=self.objective)
         elif getattr(trainer, "optimizer", "sgd") != self.optim:
             raise ValueError("args.optim is %r but the trainer steps with %r" % (self.optim, getattr(trainer, "optimizer", "sgd")))
         self.trainer = trainer
