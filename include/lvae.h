@@ -409,6 +409,25 @@ int lv_dec_tail_parts(int H);
 int lv_dec_tail_bwd_f32(const float* dGsum, const float* dc0, const float* z, const float* w_ih, long ld_wih, int col0,
                         const float* w_trans, float* gw_ih, long ld_gwih, float* gw_trans, float* gb_ih, float* gb_hh,
                         float* dz_parts, int B, int H, int nz, void* stream);
+/* the dz half of the same for a frozen decoder (VAE.refine_posterior): dz_parts [parts][B][nz] only, bit-equal to
+ * lv_dec_tail_bwd_f32's; no weight or bias gradient is formed or written */
+int lv_dec_tail_dz_f32(const float* dGsum, const float* dc0, const float* w_ih, long ld_wih, int col0, const float* w_trans,
+                       float* dz_parts, int B, int H, int nz, void* stream);
+
+/* ---- posterior refinement by SVI on the encoder's output (lv_svi.hip; Cremer et al. 2018, the inference half of SA-VAE) ---
+ * Per sentence b, phi = mulv[b] = (mu | logvar), fixed noise eps [B][ns][nz], beta = kl_weight_dev[0]:
+ *   L_b(phi) = (1/ns) sum_s rec(x_b, mu + eps_s*exp(logvar/2)) + beta * 0.5*sum_j(mu_j^2 + exp(logvar_j) - logvar_j - 1).
+ * One launch per iteration: trace_row[b] = (1/ns) sum_s rec[b*ns + s] + beta*kl[b] (the CURRENT iterate's L_b); where that is
+ * strictly below best_loss[b] it replaces it and phi is copied to best_mulv[b] (a tie keeps the earlier iterate); then, unless
+ * dz is NULL (finish mode: nothing else is read or written),
+ *   g = gradient of lv_reparam_kl_bwd_f32 with seeds dz (summed over dz_parts in order; the decoder backward carries 1/ns) and
+ *       dkl = beta;  g *= min(1, clip / (|g|_2 + 1e-6)) over the sentence's 2nz values;  vel = momentum*vel + g;
+ *   mulv -= lr*vel;  z_next [B][ns][nz], kl_next [B] = lv_reparam_kl_fwd_f32 of the updated mulv, bit for bit.
+ * rec [B*ns], kl [B]; mulv, vel, best_mulv [B][2nz] and best_loss [B] are in/out.  lr, clip > 0, 0 <= momentum < 1. */
+int lv_svi_step_f32(const float* rec, const float* dz, int dz_parts, const float* eps, const float* kl,
+                    const float* kl_weight_dev, float lr, float momentum, float clip, float* mulv, float* vel,
+                    float* best_mulv, float* best_loss, float* trace_row, float* z_next, float* kl_next, int B, int ns,
+                    int nz, void* stream);
 
 /* small elementwise / reductions used by the sequencing (h0 = tanh(c0) dec_lstm.py:100; bias grads) */
 int lv_tanh_f32(const float* in, float* out, long n, void* stream);
@@ -672,6 +691,12 @@ int lv_bn_workspace_floats(int C);
  * y = act((x - run_mean) / sqrt(run_var + eps) * gamma + beta (+ res)); mean_out / invstd_out (may be NULL) = what was applied */
 int lv_bn_eval_f32(const float* x, const float* gamma, const float* beta, const float* run_mean, const float* run_var, float eps,
                    const float* res, int act_elu, float* y, float* mean_out, float* invstd_out, long P, int C, void* stream);
+/* backward of lv_bn_eval_f32 (the statistics are constants: no batch-sum term): g = dy (+ dy2 + dy3 + dy4, NULL or given in order),
+ * dv = g * elu'(y) (also the residual input's gradient), dx = dv * gamma * invstd, dbeta = sum_p dv, dgamma = sum_p dv * xhat
+ * (= or +=); mean / invstd as lv_bn_eval_f32 wrote them */
+int lv_bn_eval_bwd_f32(const float* x, const float* dy, const float* dy2, const float* dy3, const float* dy4, const float* y,
+                       const float* mean, const float* invstd, const float* gamma, int act_elu, float* dv, float* dx,
+                       float* dgamma, float* dbeta, int accumulate_param_grads, long P, int C, void* stream);
 int lv_bn_fwd_f32(const float* x, const float* gamma, const float* beta, const float* res, int act_elu,
                   float* y, float* mean, float* invstd, float* run_mean, float* run_var,
                   float eps, float momentum, float* ws, long P, int C, void* stream);

@@ -67,6 +67,8 @@ SIGNATURES = {
     "lv_dec_tail_parts": [_i],
     "lv_dec_init_f32": [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_dec_tail_bwd_f32": [_vp, _vp, _vp, _vp, _l, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_dec_tail_dz_f32": [_vp, _vp, _vp, _l, _i, _vp, _vp, _i, _i, _i, _vp],
+    "lv_svi_step_f32": [_vp, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_clip_norm2_f32": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp],
     "lv_clip_norm2_txn_f32": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lv_clip_norm2_fold_txn_f32": [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -177,7 +179,8 @@ SIGNATURES = {
     "lv_pixelcnn_pixel_step_f32": [_vp, _i, _i, _i, _vp],
     "lv_conv32_tap_split": [_i],
     "lv_bn_eval_f32": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _l, _i, _vp],
-    "lv_bn_fwd_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _l, _i, _vp],
+    "lv_bn_eval_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _l, _i, _vp],
+    "lv_bn_fwd_f32":[_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _l, _i, _vp],
     "lv_bn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _l, _i, _vp],
     "lv_bn_bwd2_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _l, _i, _vp],
     "lv_bn_bwd4_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _l, _i, _vp],

@@ -831,6 +831,53 @@ __global__ __launch_bounds__(256) void bn_eval_kernel(const float* __restrict__ 
     }
 }
 
+// Backward of the same (the statistics are constants, so there is no batch-sum term): g = dy (+ dy2 + dy3 + dy4, in order),
+// dv = g * elu'(y) (also the gradient of the residual input), dx = dv * gamma * invstd.  One streaming pass.
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ dy2,
+                                                          const float* __restrict__ dy3, const float* __restrict__ dy4,
+                                                          const float* __restrict__ y, const float* __restrict__ invstd,
+                                                          const float* __restrict__ gamma, int act, float* __restrict__ dv,
+                                                          float* __restrict__ dx, long n, int C) {
+    const long gs = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += gs) {
+        const int c = (int)(i % C);
+        float g = dy[i];
+        if (dy2) g += dy2[i];
+        if (dy3) g += dy3[i];
+        if (dy4) g += dy4[i];
+        if (act) { const float yy = y[i]; g = yy > 0.f ? g : g * (yy + 1.f); }
+        dv[i] = g;
+        dx[i] = g * (gamma[c] * invstd[c]);
+    }
+}
+
+// ... and its affine parameters' gradients, one workgroup per channel: dbeta[c] = sum_p dv[p][c], dgamma[c] = sum_p dv[p][c] * xhat[p][c]
+// with xhat = (x - mean) * invstd; rows dealt to the threads, fixed-shape tree in LDS (deterministic)
+__global__ __launch_bounds__(256) void bn_eval_bwd_param_kernel(const float* __restrict__ x, const float* __restrict__ dv,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate,
+                                                                long P, int C) {
+    __shared__ float sb[256], sg[256];
+    const int c = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const float m = mean[c], is = invstd[c];
+    float b = 0.f, g = 0.f;
+    for (long p = tid; p < P; p += 256) {
+        const float d = dv[p * C + c];
+        b += d;
+        g += d * ((x[p * C + c] - m) * is);
+    }
+    sb[tid] = b; sg[tid] = g;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if (tid < h) { sb[tid] += sb[tid + h]; sg[tid] += sg[tid + h]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        dbeta[c] = accumulate ? dbeta[c] + sb[0] : sb[0];
+        dgamma[c] = accumulate ? dgamma[c] + sg[0] : sg[0];
+    }
+}
+
 }  // namespace
 
 // col[N*Ho*Wo][ldcol] <- the first `ntaps` raster-order taps of a kh x kw window (stride, pad) of NHWC x
@@ -898,6 +945,24 @@ extern "C" int lv_bn_eval_f32(const float* x, const float* gamma, const float* b
                       act_elu, y, mean_out, invstd_out, n, C);
     else LV_LAUNCH(bn_eval_kernel<false>, dim3(conv_grid(n)), dim3(256), 0, stream, x, gamma, beta, run_mean, run_var, eps, res, act_elu,
                    y, mean_out, invstd_out, n, C);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// Backward of lv_bn_eval_f32 (a frozen, eval-mode network differentiated with respect to its input: VAE.refine_posterior on the
+// image decoder).  mean / invstd: what lv_bn_eval_f32 left in mean_out / invstd_out; dy2 .. dy4 may be NULL (given in order); y is
+// read only with act_elu.  Writes dv, dx and dgamma / dbeta (= or +=).
+extern "C" int lv_bn_eval_bwd_f32(const float* x, const float* dy, const float* dy2, const float* dy3, const float* dy4, const float* y,
+                                  const float* mean, const float* invstd, const float* gamma, int act_elu, float* dv, float* dx,
+                                  float* dgamma, float* dbeta, int accumulate_param_grads, long P, int C, void* stream) {
+    if (!x || !dy || !mean || !invstd || !gamma || !dv || !dx || !dgamma || !dbeta) return LV_ERR_ARG;
+    if (act_elu && !y) return LV_ERR_ARG;
+    if ((dy3 && !dy2) || (dy4 && !dy3)) return LV_ERR_ARG;
+    if (P <= 0 || C <= 0) return LV_ERR_SHAPE;
+    LV_LAUNCH(bn_eval_bwd_kernel, dim3(conv_grid(P * C)), dim3(256), 0, stream, dy, dy2, dy3, dy4, y, invstd, gamma, act_elu, dv, dx,
+              P * C, C);
+    LV_LAUNCH(bn_eval_bwd_param_kernel, dim3((unsigned)C), dim3(256), 0, stream, x, (const float*)dv, mean, invstd, dgamma, dbeta,
+              accumulate_param_grads, P, C);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

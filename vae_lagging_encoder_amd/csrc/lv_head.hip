@@ -265,7 +265,10 @@ __global__ __launch_bounds__(256) void dec_init_kernel(const float* __restrict__
 //   * weight gradients: out[row][k] = sum_b d[b][row] z[b][k] (gW_ih[:, col0:] / gW_trans) -- lanes run over k, so a row's nz
 //     outputs are one contiguous store -- and the bias gradients g_bih[n] = g_bhh[n] = sum_b d[b][n];
 //   * its partial of dz: dzp[part][b][k] = sum_{rows} d[b][row] W[row][k]   (the consumer sums the parts in order).
+// DZ_ONLY (lv_dec_tail_dz_f32, the frozen-decoder refinement of DESIGN.md 3.7): the dz partials alone -- z is not staged, no
+// weight or bias gradient is formed or written (the four pointers may be null); the partials are the same sums in the same order.
 constexpr int DZ_ROWS = 64;
+template <bool DZ_ONLY>
 __global__ __launch_bounds__(256) void dec_tail_bwd_kernel(const float* __restrict__ dGsum, const float* __restrict__ dc0,
                                                            const float* __restrict__ z, const float* __restrict__ wih,
                                                            long ld_wih, int col0, const float* __restrict__ wtr,
@@ -281,7 +284,7 @@ __global__ __launch_bounds__(256) void dec_tail_bwd_kernel(const float* __restri
     const int part = (int)blockIdx.x;
     const int row0 = part * DZ_ROWS;
     const int nrows = 5 * H - row0 < DZ_ROWS ? 5 * H - row0 : DZ_ROWS;
-    stage_batched(B * nz, tid, [&](int i) { return z + i; }, [&](int i, float v) { sz[i] = v; });
+    if constexpr (!DZ_ONLY) stage_batched(B * nz, tid, [&](int i) { return z + i; }, [&](int i, float v) { sz[i] = v; });
     stage_batched(B * DZ_ROWS, tid,
                   [&](int i) {
                       const int b = i / DZ_ROWS, rr = i % DZ_ROWS;
@@ -297,19 +300,21 @@ __global__ __launch_bounds__(256) void dec_tail_bwd_kernel(const float* __restri
                   },
                   [&](int i, float v) { swt[i] = (i / nz) < nrows ? v : 0.f; });
     __syncthreads();
-    // weight gradients: (row, k) pairs dealt to the threads with k fastest
-    for (int i = tid; i < nrows * nz; i += 256) {
-        const int rr = i / nz, k = i % nz, row = row0 + rr;
-        const float sv = dot2_batched(B, [&](int b) { return sdv[b * pd + rr]; }, [&](int b) { return sz[b * nz + k]; });
-        if (row < 4 * H) gwih[(long)row * ld_gwih + col0 + k] = sv;
-        else gwtr[(long)(row - 4 * H) * nz + k] = sv;
-    }
-    for (int rr = tid; rr < nrows; rr += 256) {           // bias gradients (gate rows only)
-        const int row = row0 + rr;
-        if (row < 4 * H) {
-            float t = 0.f;
-            for (int b = 0; b < B; ++b) t += sdv[b * pd + rr];
-            gbih[row] = t; gbhh[row] = t;
+    if constexpr (!DZ_ONLY) {
+        // weight gradients: (row, k) pairs dealt to the threads with k fastest
+        for (int i = tid; i < nrows * nz; i += 256) {
+            const int rr = i / nz, k = i % nz, row = row0 + rr;
+            const float sv = dot2_batched(B, [&](int b) { return sdv[b * pd + rr]; }, [&](int b) { return sz[b * nz + k]; });
+            if (row < 4 * H) gwih[(long)row * ld_gwih + col0 + k] = sv;
+            else gwtr[(long)(row - 4 * H) * nz + k] = sv;
+        }
+        for (int rr = tid; rr < nrows; rr += 256) {           // bias gradients (gate rows only)
+            const int row = row0 + rr;
+            if (row < 4 * H) {
+                float t = 0.f;
+                for (int b = 0; b < B; ++b) t += sdv[b * pd + rr];
+                gbih[row] = t; gbhh[row] = t;
+            }
         }
     }
     // partial dz: (b, k) pairs dealt to the threads with k fastest
@@ -401,8 +406,23 @@ extern "C" int lv_dec_tail_bwd_f32(const float* dGsum, const float* dc0, const f
     const size_t sh = ((size_t)B * nz + (size_t)B * (DZ_ROWS + 1) + (size_t)DZ_ROWS * nz) * sizeof(float);
     if (sh > 64000) return LV_ERR_UNSUPPORTED;
     const int parts = lv_cdiv(5L * H, DZ_ROWS);
-    LV_LAUNCH(dec_tail_bwd_kernel, dim3((unsigned)parts), dim3(256), sh, stream, dGsum, dc0, z, wih, ld_wih, col0, wtr, gwih,
+    LV_LAUNCH(dec_tail_bwd_kernel<false>, dim3((unsigned)parts), dim3(256), sh, stream, dGsum, dc0, z, wih, ld_wih, col0, wtr, gwih,
               ld_gwih, gwtr, gbih, gbhh, dz_parts, B, H, nz);
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// The dz half of lv_dec_tail_bwd_f32 for a frozen decoder (posterior refinement): dz_parts [parts][B][nz] only,
+// bit-equal to what lv_dec_tail_bwd_f32 writes there; no weight or bias gradient is formed.  Same LDS envelope.
+extern "C" int lv_dec_tail_dz_f32(const float* dGsum, const float* dc0, const float* wih, long ld_wih, int col0, const float* wtr,
+                                  float* dz_parts, int B, int H, int nz, void* stream) {
+    if (!dGsum || !dc0 || !wih || !wtr || !dz_parts) return LV_ERR_ARG;
+    if (B <= 0 || H <= 0 || nz <= 0 || ld_wih < col0 + nz) return LV_ERR_SHAPE;
+    const size_t sh = ((size_t)B * nz + (size_t)B * (DZ_ROWS + 1) + (size_t)DZ_ROWS * nz) * sizeof(float);
+    if (sh > 64000) return LV_ERR_UNSUPPORTED;
+    const int parts = lv_cdiv(5L * H, DZ_ROWS);
+    LV_LAUNCH(dec_tail_bwd_kernel<true>, dim3((unsigned)parts), dim3(256), sh, stream, dGsum, dc0, (const float*)nullptr, wih, ld_wih,
+              col0, wtr, (float*)nullptr, 0L, (float*)nullptr, (float*)nullptr, (float*)nullptr, dz_parts, B, H, nz);
     LV_CHECK_LAUNCH();
     return LV_OK;
 }

@@ -1842,12 +1842,7 @@ class LSTMDecoderEngine(object):
         pad_idx = self.m.embed.padding_idx
         pad_idx = V - 1 if pad_idx is None else int(pad_idx)
         b16 = self._b16(Bd, Td, ns)
-        if b16 is not None and self.fused_nll:
-            lib.lv_softmax_nll_bwd_h16(P(b16.l16), b16.ldv, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
-        elif b16 is not None:
-            lib.lv_softmax_nll_bwd_b16(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
-        else:
-            lib.lv_softmax_nll_bwd_f32(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), Td, Bd, V, s)
+        self._bwd_dlogits(lib, s, w, b16, ids, drec, T, Td, Bd, V)
         ctx, sws = self._fork(dev)                    # side: dW_pred = dlogits^T . O (only needs dlogits and O)
         with ctx:
             if b16 is not None and self.fold and "pred" in self.fold:
@@ -1865,23 +1860,7 @@ class LSTMDecoderEngine(object):
                 _wgrad(lib, stream_ptr(dev), V, H, Td * Bd, P(w.logits), w.ldl, P(w.O), H, P(gv["pred_linear.weight"]), H,
                        self.precision, ws=sws)
         img = self._lstm_images(Bd, Td, ns)
-        late_mask = _persistent_ok(self, img, Bd, H, dev, _PERSIST_BWD_MAX_B)
-        if b16 is not None and late_mask and mask_out is not None:
-            # dO = dlogits . W_pred with the dropout_out backward applied where the product's K pieces are summed (no pass of its own)
-            gws = _gemm_ws(lib, s)
-            with _prof("gemm_bf16", 2.0 * Td * Bd * H * V):
-                lib.lv_gemm_b16_keep(Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), P(mask_out), sc_out, Bd,
-                                     P(gws), gws.numel(), s)
-        else:
-            if b16 is not None:
-                _gemm16(lib, s, 0, Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), H)
-            else:
-                _gemm(lib, s, 0, 0, Td * Bd, H, V, P(w.logits), w.ldl, P(v["pred_linear.weight"]), H, P(w.dO), H, prec=self.precision)
-            if late_mask and mask_out is not None:
-                lib.lv_keep_scale_f32(P(w.dO), P(mask_out), sc_out, Td, Bd, H, s)      # dropout_out backward, once, loads along H
-        with _prof("lstm_bwd_dec", float(Td), 1 if late_mask else 2 * Td):
-            _lstm_backward(self, lib, s, img, w, P(w.dO), None, None if late_mask else P(mask_out), 1.0 if late_mask else sc_out,
-                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, Bd, H, dev, steps=getattr(self, "last_steps", None))
+        self._bwd_dO_bptt(lib, s, w, b16, img, mask_out, sc_out, Td, Bd, V, H, dev)
         ctx, sws = self._fork(dev)                    # side: everything that only needs dG (runs under the encoder's backward)
         with ctx:
             s2 = stream_ptr(dev)
@@ -1922,6 +1901,172 @@ class LSTMDecoderEngine(object):
             return w.dzp, w.dz_parts         # the fused driver's encoder head sums the parts itself
         lib.lv_colsum_f32(P(w.dzp), Bd * nz, w.dz_parts, Bd * nz, P(w.dz), None, s)
         return w.dz
+
+    # ---- the chain that reaches dz, shared by backward() and backward_dz() -----------------------------------------------------
+    def _bwd_dlogits(self, lib, s, w, b16, ids, drec, T, Td, Bd, V):
+        """dlogits = (softmax - onehot) * drec[row], in the form the route's dO product reads."""
+        if b16 is not None and self.fused_nll:
+            lib.lv_softmax_nll_bwd_h16(P(b16.l16), b16.ldv, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
+        elif b16 is not None:
+            lib.lv_softmax_nll_bwd_b16(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), P(b16.dl), b16.ldv, Td, Bd, V, s)
+        else:
+            lib.lv_softmax_nll_bwd_f32(P(w.logits), w.ldl, P(w.lse), P(ids), T, 1, P(drec), Td, Bd, V, s)
+
+    def _bwd_dO_bptt(self, lib, s, w, b16, img, mask_out, sc_out, Td, Bd, V, H, dev):
+        """dO = dlogits . W_pred (dropout_out backward included), then the BPTT: leaves dG (or its bf16 image), dGsum and dc0."""
+        v = self.flat.views
+        late_mask = _persistent_ok(self, img, Bd, H, dev, _PERSIST_BWD_MAX_B)
+        if b16 is not None and late_mask and mask_out is not None:
+            # dO = dlogits . W_pred with the dropout_out backward applied where the product's K pieces are summed (no pass of its own)
+            gws = _gemm_ws(lib, s)
+            with _prof("gemm_bf16", 2.0 * Td * Bd * H * V):
+                lib.lv_gemm_b16_keep(Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), P(mask_out), sc_out, Bd,
+                                     P(gws), gws.numel(), s)
+        else:
+            if b16 is not None:
+                _gemm16(lib, s, 0, Td * Bd, H, V, P(b16.dl), b16.ldv, P(self._wimg.predT), b16.ldv, P(w.dO), H)
+            else:
+                _gemm(lib, s, 0, 0, Td * Bd, H, V, P(w.logits), w.ldl, P(v["pred_linear.weight"]), H, P(w.dO), H, prec=self.precision)
+            if late_mask and mask_out is not None:
+                lib.lv_keep_scale_f32(P(w.dO), P(mask_out), sc_out, Td, Bd, H, s)      # dropout_out backward, once, loads along H
+        with _prof("lstm_bwd_dec", float(Td), 1 if late_mask else 2 * Td):
+            _lstm_backward(self, lib, s, img, w, P(w.dO), None, None if late_mask else P(mask_out), 1.0 if late_mask else sc_out,
+                           P(v["lstm.weight_hh_l0"]), None, P(w.dc0), 1, Td, Bd, H, dev, steps=getattr(self, "last_steps", None))
+
+    def _bwd_tail_dz(self, lib, s, w, Bd, H, ni, nz, partial_dz):
+        """dz = dGsum . W_ih[:, ni:] + dc0 . W_trans and nothing else (lv_dec_tail_dz_f32; the two products beyond its envelope)."""
+        v = self.flat.views
+        wih = v["lstm.weight_ih_l0"]
+        if not fused_ends_ok(Bd, nz):
+            _gemm(lib, s, 0, 0, Bd, nz, 4 * H, P(w.dGsum), 4 * H, P(wih, ni), ni + nz, P(w.dz), nz)
+            _gemm(lib, s, 0, 0, Bd, nz, H, P(w.dc0), H, P(v["trans_linear.weight"]), nz, P(w.dz), nz, acc=1)
+            return (w.dz, 1) if partial_dz else w.dz
+        lib.lv_dec_tail_dz_f32(P(w.dGsum), P(w.dc0), P(wih), ni + nz, ni, P(v["trans_linear.weight"]), P(w.dzp), Bd, H, nz, s)
+        if partial_dz:
+            return w.dzp, w.dz_parts
+        lib.lv_colsum_f32(P(w.dzp), Bd * nz, w.dz_parts, Bd * nz, P(w.dz), None, s)
+        return w.dz
+
+    def backward_dz(self, drec, gen=None, partial_dz=False):
+        """backward() for a FROZEN decoder: drec [B*ns] -> dz [B*ns][nz] (partial_dz: as backward()), through the same
+        launches on the chain that reaches dz -- softmax backward, dO = dlogits . W_pred, BPTT, the dz tail -- and nothing else: no
+        weight-gradient product, no dX, no embedding scatter, no write to flat.grad.  In f32 dz is bit-equal to backward()'s."""
+        x, z2, mask_in, mask_out, sc_in, sc_out, B, T, g = self.last
+        if gen is not None and gen != g:
+            raise _lib.LvaeError("decoder activations were overwritten by a later forward(); the HIP engine keeps "
+                                 "one in-flight step per module")
+        ns = self.last_ns
+        Bd, Td = B * ns, T - 1
+        lib, s = self.lib, stream_ptr(x.device)
+        V, ni, H, nz = self.dims()
+        w = self._ws(Bd, Td, ns)
+        drec = drec.contiguous()
+        if drec.numel() != Bd:
+            raise _lib.LvaeError("backward_dz takes drec per decoder row (%d values for %d samples per sentence), got %d" % (Bd, ns, drec.numel()))
+        b16 = self._b16(Bd, Td, ns)
+        self._bwd_dlogits(lib, s, w, b16, x if ns == 1 else w.x_rep, drec, T, Td, Bd, V)
+        self._bwd_dO_bptt(lib, s, w, b16, self._lstm_images(Bd, Td, ns), mask_out, sc_out, Td, Bd, V, H, x.device)
+        return self._bwd_tail_dz(lib, s, w, Bd, H, ni, nz, partial_dz)
+
+    # ---- posterior refinement (VAE.refine_posterior, DESIGN.md 3.7) ----------------------------------------------------------------
+    def svi_supported(self, B, ns):
+        """The refinement session's envelope: lv_dec_init_f32 / lv_dec_tail_dz_f32's LDS budget on the B * ns decoder rows."""
+        return fused_ends_ok(B * ns, self.dims()[3])
+
+    def _svi_ws(self, B, ns, Td):
+        V, ni, H, nz = self.dims()
+        c = self.wsc
+
+        def build():
+            sv = _NS()
+            sv.Gxw = c.f32(Td * B, 4 * H)                  # X . W_ih[:, :ni]^T, one row per (t, sentence): computed once per call
+            sv.z = c.f32(B * ns, nz)
+            sv.kl = [c.f32(B), c.f32(B)]
+            sv.klw = c.f32(1)
+            sv.rowscale = c.f32(B * ns)
+            return sv
+        return c.get(("svi", B, ns, Td), build)
+
+    def svi_refine(self, x, mulv, eps, steps, lr, momentum, clip, kl_weight):
+        """`steps` SVI iterations on every sentence's phi = (mu | logvar) with this decoder frozen and in eval arithmetic (no dropout):
+        x int64 [B][T], mulv [B][2nz] (the starting point; not modified), eps [B][ns][nz] (the same in every iteration).  steps + 1
+        forwards, steps backwards to z.  -> dict(last [B][2nz], best [B][2nz], best_loss [B], trace, rec_trace, kl_trace
+        [steps+1][B]: L_b(phi_k) and its two terms, the sample-mean reconstruction error and the analytic KL).  Nothing is read back to the host; the caller checks svi_supported().
+
+        Exact-f32 configuration: the z-independent work -- embedding gather, the word half of the input projection, the targets in
+        decoder row order -- runs once; an iteration is lv_dec_init_f32, lv_gx_expand_add_f32, the recurrence, the vocabulary
+        projection + NLL, the softmax backward, dO, the BPTT, lv_dec_tail_dz_f32 and lv_svi_step_f32.  bf16: an iteration runs
+        forward() as it is (step / persistent recurrences, images and all; its gather and input projection are repeated) and
+        backward_dz()."""
+        steps = int(steps)
+        x = x.contiguous()
+        B, T = x.shape
+        Td = T - 1
+        dev = x.device
+        _same_device("svi_refine", dev, mulv=mulv, eps=eps)
+        f = self.ensure(dev)
+        V, ni, H, nz = self.dims()
+        if tuple(mulv.shape) != (B, 2 * nz) or eps.dim() != 3 or eps.shape[0] != B or eps.shape[2] != nz or eps.shape[1] < 1:
+            raise ValueError("svi_refine: mulv [%d][%d] and eps [%d][ns][%d] expected, got %s and %s"
+                             % (B, 2 * nz, B, nz, tuple(mulv.shape), tuple(eps.shape)))
+        ns = int(eps.shape[1])
+        Bd = B * ns
+        lib, s = self.lib, stream_ptr(dev)
+        v = f.views
+        eps = eps.detach().float().contiguous()
+        exact = self.precision == "f32"
+        sv = self._svi_ws(B, ns, Td)
+        f32 = dict(dtype=torch.float32, device=dev)
+        phi = mulv.detach().float().contiguous().clone()
+        vel = torch.zeros(B, 2 * nz, **f32)
+        best = phi.clone()
+        best_loss = torch.full((B,), float("inf"), **f32)
+        trace = torch.empty(steps + 1, B, **f32)
+        rec_trace, kl_trace = torch.empty_like(trace), torch.empty_like(trace)     # the two terms of L_b(phi_k), for the report
+        sv.klw.fill_(float(kl_weight))
+        sv.rowscale.fill_(1.0 / ns)
+        w = self._ws(Bd, Td, ns)
+        wih = v["lstm.weight_ih_l0"]
+        ids = x
+        if exact:
+            lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, None, 1.0, P(w.X), Td, B, ni, V, s)
+            _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(wih), ni + nz, P(sv.Gxw), 4 * H, prec=self.precision)
+            if ns > 1:
+                lib.lv_repeat_rows_i64(P(x), P(w.x_rep), B, T, ns, s)
+                ids = w.x_rep
+            _gx_buffer(self.wsc, w, Td * Bd, H)
+            self.last_steps = None                     # equal-length BPTT, whatever the last forward() was given
+        kl, kl_next = sv.kl
+        lib.lv_reparam_kl_fwd_f32(P(phi), P(eps), P(sv.z), P(kl), B, ns, nz, s)
+        for k in range(steps + 1):
+            if exact:
+                lib.lv_dec_init_f32(P(sv.z), P(v["trans_linear.weight"]), P(wih), ni + nz, ni, P(v["lstm.bias_ih_l0"]),
+                                    P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 0, Bd, H, nz, s)
+                lib.lv_gx_expand_add_f32(P(sv.Gxw), P(w.Zp), P(w.Gx), Td, B, ns, 4 * H, s)
+                _lstm_forward(self, lib, s, None, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, P(w.O), Td, Bd, H, dev)
+                _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
+                lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
+                lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
+            else:
+                self.forward(x, sv.z.view(B, ns, nz), None, None, 0.0, 0.0)
+            torch.sum(w.rec.view(B, ns), dim=1, out=rec_trace[k])
+            rec_trace[k].div_(ns)
+            kl_trace[k].copy_(kl)
+            if k == steps:
+                lib.lv_svi_step_f32(P(w.rec), None, 0, None, P(kl), P(sv.klw), float(lr), float(momentum), float(clip), P(phi), None,
+                                    P(best), P(best_loss), P(trace, k * B), None, None, B, ns, nz, s)
+                break
+            if exact:
+                self._bwd_dlogits(lib, s, w, None, ids, sv.rowscale, T, Td, Bd, V)
+                self._bwd_dO_bptt(lib, s, w, None, None, None, 1.0, Td, Bd, V, H, dev)
+                dzp, parts = self._bwd_tail_dz(lib, s, w, Bd, H, ni, nz, True)
+            else:
+                dzp, parts = self.backward_dz(sv.rowscale, partial_dz=True)
+            lib.lv_svi_step_f32(P(w.rec), P(dzp), parts, P(eps), P(kl), P(sv.klw), float(lr), float(momentum), float(clip), P(phi),
+                                P(vel), P(best), P(best_loss), P(trace, k * B), P(sv.z), P(kl_next), B, ns, nz, s)
+            kl, kl_next = kl_next, kl
+        self.gen += 1                                  # the workspaces no longer hold what the last forward() left
+        return {"last": phi, "best": best, "best_loss": best_loss, "trace": trace, "rec_trace": rec_trace, "kl_trace": kl_trace}
 
 
 def fused_ends_ok(B, nz, ns=1):

@@ -94,6 +94,35 @@ def calc_au(model, test_data_batch, delta=0.01):
     return int((au_var >= delta).sum().item()), au_var
 
 
+def calc_amortization_gap(model, test_data_batch, steps=20, nsamples=1, np_rng=None, **refine_kwargs):
+    """The amortization gap (Cremer et al. 2018) in nats per sentence over the batches: ELBO of the posterior refined by `steps`
+    SVI steps on the encoder's output (VAE.refine_posterior) minus ELBO of the encoder's own posterior, both evaluated on the SAME
+    noise (the refinement's trace holds both), ELBO = -(rec + kl_weight * KL).  With keep = "best" (the default) gap >= 0.  The
+    batches are visited in a random order as calc_iwnll visits them (the order decides which draws each batch sees).
+    Returns dict(elbo_enc, elbo_svi, gap, n); refine_kwargs go to refine_posterior (lr, momentum, clip, kl_weight, generator, keep)."""
+    order = (np_rng if np_rng is not None else np.random).permutation(len(test_data_batch))
+    return _amortization_gap(model, (test_data_batch[i] for i in order), steps, nsamples, refine_kwargs)
+
+
+def _amortization_gap(model, batches, steps, nsamples, refine_kwargs):
+    enc, svi = [], []
+    n = 0
+    for batch_data in batches:
+        info = model.refine_posterior(batch_data, steps=steps, nsamples=nsamples, return_info=True, **refine_kwargs)[2]
+        enc.append(info["loss0"].sum())
+        svi.append(info["loss"].sum())
+        n += batch_data.size(0)
+    elbo_enc = -float(torch.stack(enc).sum().item()) / n
+    elbo_svi = -float(torch.stack(svi).sum().item()) / n
+    return {"elbo_enc": elbo_enc, "elbo_svi": elbo_svi, "gap": elbo_svi - elbo_enc, "n": n}
+
+
+def image_calc_amortization_gap(model, test_loader, steps=20, nsamples=1, **refine_kwargs):
+    """calc_amortization_gap over one pass of a loader of (batch, label) pairs, in nats per image (the generic route of
+    VAE.refine_posterior: the eval-mode PixelCNN decoder differentiated with respect to z)."""
+    return _amortization_gap(model, (batch_data for batch_data, _ in test_loader), steps, nsamples, refine_kwargs)
+
+
 # ---- image side (reference image.py:96-187): the loaders yield (batch, label) pairs like DataLoader(TensorDataset(x, y)) --------
 def image_test(model, test_loader, mode, args=None, verbose=True):
     """image.py:96-128: loss / KL / reconstruction over one pass of the loader (eval mode is the caller's), then calc_mi over a

@@ -397,6 +397,16 @@ class Tape(object):
                 return
             dys = [P(t_) for t_ in terms] + [None] * (4 - len(terms))
             dv = self.f32(Pn, C)
+            if not self.train:
+                # eval-mode forward (running statistics are constants): no batch-sum term in dx
+                with _eng._prof("batchnorm", 4.0 * Pn * C * (4 + len(terms))):
+                    lib.lv_bn_eval_bwd_f32(P(x.t), dys[0], dys[1], dys[2], dys[3], P(y), P(mean), P(invstd), P(bn.weight), int(act), P(dv),
+                                           P(dx), P(g_gamma), P(g_beta), 0, Pn, C, s)
+                if res is not None and res.needs_grad:
+                    self.add_grad(res, dv)
+                if x.needs_grad:
+                    self.add_grad(x, dx)
+                return
             # reduce pass: x, y, the summands in, dv out; apply pass: x, dv in, dx out
             with _eng._prof("batchnorm", 4.0 * Pn * C * (6 + len(terms))):
                 lib.lv_bn_bwd4_f32(P(x.t), dys[0], dys[1], dys[2], dys[3], P(y), P(mean), P(invstd), P(bn.weight), int(act), P(dv), P(dx),

@@ -387,6 +387,144 @@ class VAE(nn.Module):
                          flag_out=flags[it])
         return samples, cur_ll, accepts, ratios, flags
 
+    # True: refine_posterior takes the engine's refinement session (lv_svi_step_f32, lv_dec_tail_dz_f32) where _fused_svi_ok
+    # allows it; False forces the generic route (A/B runs, the tests' second oracle, the bench baseline)
+    fused_svi = True
+
+    def _fused_svi_ok(self, x, B, ns):
+        """Route "fused" of refine_posterior, in the style of _fused_mh_ok: an LSTM decoder, x a 2-D int64 tensor on a device the
+        package has kernels for, B * ns decoder rows inside the LDS budget of the decoder's batch-sized ends."""
+        eng = getattr(self.decoder, "_hip", None)
+        if not (self.fused_svi and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.int64):
+            return False
+        try:
+            eng.ensure(x.device)
+        except _lib.LvaeError:
+            return False
+        return eng.svi_supported(B, ns)
+
+    def refine_posterior(self, x, steps=20, lr=1.0, momentum=0.5, clip=5.0, kl_weight=1.0, nsamples=1, noise=None, generator=None,
+                         keep="best", return_info=False):
+        """Stochastic variational inference on the encoder's output (Cremer et al. 2018; the inference half of SA-VAE, Kim et al.
+        2018) -> (mu, logvar), each (batch, nz), detached.  The decoder is frozen and runs in eval arithmetic (no dropout) whatever
+        `training` says; each sentence's phi = (mu, logvar) starts at the encoder's values and takes `steps` steps on its own
+            L_b(phi) = (1/ns) sum_s rec(x_b, mu + eps_s * exp(logvar / 2)) + kl_weight * KL(phi)
+        with the noise eps held fixed over the iterations (L_b is then a deterministic function of phi):
+            g = grad L_b;  g *= min(1, clip / (|g|_2 + 1e-6)) (norm over the sentence's 2 nz values);  v = momentum * v + g;
+            phi -= lr * v.
+        steps = K costs K + 1 decoder forwards and K backwards to z.  keep = "best": the iterate with the smallest L_b (the earliest
+        on a tie); "last": phi_K.  L_b(encoder) - L_b(refined) is the sentence's amortization gap (evaluation.calc_amortization_gap).
+
+        noise: eps (batch, nsamples, nz) float32 on x's device; otherwise drawn once with torch.randn on x's device (`generator`
+        optional).  Nothing of the model changes: parameters, gradients (.grad and the engines' flat buffers), buffers and the
+        training flags are as before, and with `noise` given so is every RNG state.
+
+        Routes (class switch fused_svi = False forces the second):
+          "fused":   LSTM decoder -- engine.LSTMDecoderEngine.svi_refine: everything that does not depend on z once per call, per
+                     iteration no weight-gradient product, no dX, no embedding scatter;
+          "generic": PixelCNNDecoderV2 (its eval-mode BatchNorm backward: lv_bn_eval_bwd_f32), batches beyond the fused envelope,
+                     the second oracle and the bench baseline: per iteration decoder.reconstruct_error under eval, its autograd
+                     backward (weight gradients land in scratch that is restored afterwards), lv_reparam_kl_bwd_f32 and the
+                     update in torch.
+        return_info: also {"trace": [steps+1, batch] (L_b of phi_0 .. phi_K), "loss0", "loss", "kl", "rec" (L_b, analytic KL and
+        sample-mean reconstruction term of the returned iterate, as the loop computed them), "route"}."""
+        steps, nsamples = int(steps), int(nsamples)
+        lr, momentum, clip, kl_weight = float(lr), float(momentum), float(clip), float(kl_weight)
+        if steps < 0 or nsamples < 1:
+            raise ValueError("refine_posterior: steps >= 0 and nsamples >= 1 expected")
+        if not (lr > 0.0 and clip > 0.0 and 0.0 <= momentum < 1.0):
+            raise ValueError("refine_posterior: lr > 0, clip > 0 and 0 <= momentum < 1 expected")
+        if keep not in ("best", "last"):
+            raise ValueError("refine_posterior: keep is 'best' or 'last'")
+        if isinstance(x, (tuple, list)):
+            raise ValueError("refine_posterior: variable-length batches (x, lengths) are not supported; batch by length")
+        B, dev = x.size(0), x.device
+        if noise is not None:
+            if not torch.is_tensor(noise) or tuple(noise.shape) != (B, nsamples, self.nz) or noise.dtype != torch.float32 \
+                    or noise.device != dev:
+                raise ValueError("refine_posterior: noise must be a float32 tensor of shape (%d, %d, %d) on %s" % (B, nsamples, self.nz, dev))
+        flags = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            with torch.no_grad():
+                mulv0 = self.encoder._forward_mulv(x).detach().float().contiguous()
+                if steps == 0 and not return_info:          # nothing to evaluate: no noise is drawn
+                    return mulv0[:, :self.nz].clone(), mulv0[:, self.nz:].clone()
+                eps = noise.contiguous() if noise is not None else torch.randn(B, nsamples, self.nz, device=dev, generator=generator)
+                if self._fused_svi_ok(x, B, nsamples):
+                    route = "fused"
+                    eng = self.decoder._hip
+                    r = eng.svi_refine(x, mulv0, eps, steps, lr, momentum, clip, kl_weight)
+                    _eng.check_persistent_status(eng)       # a timed-out persistent launch: no half-refined result
+                else:
+                    route = "generic"
+                    r = self._svi_generic(x, mulv0, eps, steps, lr, momentum, clip, kl_weight)
+        finally:
+            for m, t in flags:
+                m.training = t
+        trace = r["trace"]
+        if keep == "best":
+            mulv, loss = r["best"], r["best_loss"]
+        else:
+            mulv, loss = r["last"], trace[steps]
+        mu, logvar = mulv[:, :self.nz].clone(), mulv[:, self.nz:].clone()
+        if not return_info:
+            return mu, logvar
+        # rec / kl of the returned iterate as the loop saw them (argmin: the first minimum, the iterate the strict '<' kept)
+        k = trace.argmin(dim=0, keepdim=True) if keep == "best" else torch.full((1, B), steps, dtype=torch.int64, device=dev)
+        return mu, logvar, {"trace": trace, "loss0": trace[0].clone(), "loss": loss, "kl": r["kl_trace"].gather(0, k)[0],
+                            "rec": r["rec_trace"].gather(0, k)[0], "route": route}
+
+    def _svi_generic(self, x, mulv0, eps, steps, lr, momentum, clip, kl_weight):
+        """Route "generic" of refine_posterior, from what every decoder has: reconstruct_error and its autograd backward for dz,
+        lv_reparam_kl_fwd/bwd_f32 for the variational side, the update in torch.  The decoder's weight gradients are by-products:
+        its engine's flat gradient buffers are saved before and restored after, and the parameters' .grad are not touched
+        (torch.autograd.grad asks for dz only)."""
+        B, ns = eps.shape[0], eps.shape[1]
+        dev = mulv0.device
+        eng = getattr(self.decoder, "_hip", None)
+        if hasattr(eng, "ensure"):
+            eng.ensure(dev)
+        flat = getattr(eng, "flat", None)
+        grads = [(p, p.grad) for p in self.decoder.parameters()]
+        saved = [s[0].clone() for s in flat._slots] if flat is not None else None
+        detached = getattr(flat, "detached", None)
+        phi = mulv0.clone()
+        vel = torch.zeros_like(phi)
+        best = phi.clone()
+        best_loss = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+        trace = torch.empty(steps + 1, B, dtype=torch.float32, device=dev)
+        rec_trace, kl_trace = torch.empty_like(trace), torch.empty_like(trace)
+        dkl = torch.full((B,), kl_weight, dtype=torch.float32, device=dev)
+        try:
+            for k in range(steps + 1):
+                z, kl = _eng.reparam_kl_forward(phi, eps)
+                with torch.enable_grad():
+                    z = z.detach().requires_grad_(k < steps)
+                    rec_s = self.decoder.reconstruct_error(x, z)
+                    dz = torch.autograd.grad(rec_s, z, torch.full_like(rec_s, 1.0 / ns))[0] if k < steps else None
+                rec = rec_s.detach().sum(dim=1) / ns
+                loss = rec + kl_weight * kl
+                trace[k], rec_trace[k], kl_trace[k] = loss, rec, kl
+                better = loss < best_loss
+                best = torch.where(better.unsqueeze(1), phi, best)
+                best_loss = torch.where(better, loss, best_loss)
+                if k == steps:
+                    break
+                g = _eng.reparam_kl_backward(phi, eps, dz.contiguous(), dkl)
+                g = g * torch.clamp(clip / (g.norm(dim=1, keepdim=True) + 1e-6), max=1.0)
+                vel = momentum * vel + g
+                phi = phi - lr * vel
+        finally:
+            if saved is not None:
+                for slot, keep_ in zip(flat._slots, saved):
+                    slot[0].copy_(keep_)
+                flat.detached = detached
+            for p, g0 in grads:
+                p.grad = g0
+        return {"last": phi, "best": best, "best_loss": best_loss, "trace": trace, "rec_trace": rec_trace, "kl_trace": kl_trace}
+
     def calc_infer_mean(self, x):
         return self.encoder.forward(x)[0]
 
