@@ -1,7 +1,7 @@
 #!/bin/bash
 # builds profiles/microbench/liblvae_p16<name>.so = the product library with lv_lstm_persist16.hip alone recompiled under extra -D flags
 # (the other objects come from csrc/build/: run `python -m vae_lagging_encoder_amd.build` first).  Measurement only, git-ignored.
-#   usage: build_p16_variant.sh abl66 -DLV_P16_ABL=66
+#   usage: build_p16_variant.sh abl2 -DLV_P16_ABL=2
 cd "$(dirname "$0")/../.."
 NAME=$1; shift
 C=vae_lagging_encoder_amd/csrc

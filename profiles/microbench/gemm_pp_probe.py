@@ -1,7 +1,7 @@
 """Microbenchmark (measurement tooling): the 256 x 256 bf16 GEMM kernel, lockstep K loop (tile code 256) against the ping-pong
 schedule (257: the two waves of a SIMD half a k-step apart), on the step's three vocabulary-sized products, the fused logits + NLL
 form and two squares.  Every library named in LVAE_PROBE_LIBS (comma-separated paths of alternative builds, e.g. made with
-build_alt.sh -DLV_B16_PP_DMA=1 -o ...) is timed beside the product build, columns interleaved and repeated (the first timing of a
+build_alt.sh -DLV_B16_PP_ABL=1 -o ...) is timed beside the product build, columns interleaved and repeated (the first timing of a
 kernel in a process runs slow)."""
 import ctypes
 import os

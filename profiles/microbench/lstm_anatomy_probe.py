@@ -14,12 +14,7 @@ dev = torch.device("cuda:0"); s = stream_ptr(dev)
 H = 1024
 NAMES = {0: "product kernel", 1: "no MFMAs", 2: "no waiting for producers", 3: "no MFMAs, no waiting", 4: "no transcendental math",
          6: "no waiting, no transcendental math", 7: "no MFMAs, no waiting, no transcendental math", 8: "no workgroup barrier",
-         10: "no waiting, no barrier", 15: "none of the four (loads, LDS traffic, stores, loop)",
-         16: "gathered granules not staged through LDS (fwd)", 18: "no waiting, no LDS staging of the gather (fwd)",
-         32: "h granules not loaded (fwd)", 34: "no waiting, h granules not loaded (fwd)",
-         50: "no waiting, no granule loads, no LDS staging (fwd)",
-         64: "BPTT exchange as 16-byte accesses (what-if: half the load / store instructions; tags not tested)",
-         66: "no waiting + BPTT exchange as 16-byte accesses", 63: "none of the six (fwd: Gx loads, quarter-sum LDS, stores, loop)"}
+         10: "no waiting, no barrier", 15: "none of the four (loads, LDS traffic, stores, loop)"}
 
 
 def timeit(f, n=20):
@@ -59,11 +54,8 @@ def slopes(lib, B, R, f16):
     return (res[200][0] - res[40][0]) / 160.0, (res[200][1] - res[40][1]) / 160.0
 
 
-KNOBS = {"sbb4": "LV_SBB16=4 (BPTT input block: 4 timesteps; shipped 8)", "sbb2": "LV_SBB16=2", "sbb16": "LV_SBB16=16 (spills: 1040 B/lane)",
-         "hb4sbb4": "LV_HB16=4 LV_SBB16=4 (one receive round of 32 granules per lane)", "hb1": "LV_HB16=1 (four receive rounds)",
-         "sbk2": "LV_SBK16=2 (forward I/O block: 2 timesteps; shipped 4)", "sbk8": "LV_SBK16=8 (spills: 60 B/lane)",
-         "gj8": "LV_GJ16=8 (forward: 8 granules per lane per poll round; shipped 16)", "gj32": "LV_GJ16=32 (one poll round)"}
-variants = [(int(a) if a.isdigit() else a) for a in sys.argv[1:]] or [0, 1, 2, 3, 4, 6, 7, 8, 10, 15, 16, 18, 32, 34, 50, 63]
+# arguments: what-if masks (liblvae_p16abl<N>.so) or names of other builds made with build_p16_variant.sh (liblvae_p16<name>.so)
+variants = [(int(a) if a.isdigit() else a) for a in sys.argv[1:]] or [0, 1, 2, 3, 4, 6, 7, 8, 10, 15]
 print("what-if builds of the final persistent kernels (-DLV_P16_ABL=N): microseconds per timestep, slope between T = 40 and T = 200")
 print("%-58s | %-23s | %-23s" % ("variant", "B = 32, 4 rows / group", "B = 128, 16 rows / group"))
 print("%-58s | %-11s %-11s | %-11s %-11s" % ("", "forward", "BPTT", "forward", "BPTT"))
@@ -73,7 +65,7 @@ for tag, lib in [("shipped library (liblvae_hip.so)", prod)] + [(None, v) for v 
         path = os.path.join(here, ("liblvae_p16abl%d.so" % lib) if isinstance(lib, int) else ("liblvae_p16%s.so" % lib))
         if not os.path.exists(path):
             continue
-        tag = ("ABL=%-2d %s" % (lib, NAMES.get(lib, ""))) if isinstance(lib, int) else KNOBS.get(lib, lib)
+        tag = ("ABL=%-2d %s" % (lib, NAMES.get(lib, ""))) if isinstance(lib, int) else lib
         lib = _lib.bind(ctypes.CDLL(path), path)
     a = slopes(lib, 32, 4, True)
     b = slopes(lib, 128, 16, True)

@@ -26,7 +26,6 @@ static inline unsigned long long lv_agent_load_u64(const unsigned long long* p) 
 }
 static inline void lv_agent_store_u64(unsigned long long* p, unsigned long long v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
 static inline void lv_xcd_store_u64(unsigned long long* p, unsigned long long v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-static inline void lv_poll_backoff() { }
 #define LV_WAIT_LDS() lv_emu::wave_sync()      // lanes are fibers here: 'the wave's own LDS writes are visible' needs a rendezvous
 template <class T> static inline void lv_store_nt(T v, T* p) { *p = v; }
 static inline int lv_device_cus() { return 1 << 20; }
@@ -127,7 +126,6 @@ static inline float lv_f16_bits_to_f32(uint16_t h) {
 }
 // the value held by lane (l ^ 1)
 static inline float lv_lane_xor1(float v) { return __shfl_xor(v, 1, 64); }
-static inline uint32_t lv_lane_xor1_u32(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 1, 64); }
 // the value held by lane I of this lane's quad (lanes 4q .. 4q + 3)
 template <int I> static inline uint32_t lv_quad_bcast_u32(uint32_t v) { return (uint32_t)lv_emu_xchg((int)v, (lv_emu::lane() & ~3) + I); }
 // x + (the value of lane l ^ 16) / (l ^ 32): one step of a butterfly sum across a wave's 16-lane rows / its two halves
@@ -446,9 +444,6 @@ __device__ __forceinline__ float lv_lane_xor1(float v) {
     const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true);
     return __builtin_bit_cast(float, r);
 }
-__device__ __forceinline__ uint32_t lv_lane_xor1_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
-}
 // the value held by lane I of this lane's quad (DPP quad_perm:[I, I, I, I])
 template <int I> __device__ __forceinline__ uint32_t lv_quad_bcast_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, I * 0x55, 0xF, 0xF, true);
@@ -558,16 +553,9 @@ __device__ __forceinline__ void lv_agent_store_q4(void* p, uint4 v) {
     const lv_u32x4v d = {v.x, v.y, v.z, v.w};
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
 }
-#ifndef LV_POLL_SLEEP
-#define LV_POLL_SLEEP 0                     // measurement knob: s_sleep units (64 cycles) after a FAILED poll of a hand-off, before the next one
-#endif
-__device__ __forceinline__ void lv_poll_backoff() { if (LV_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(LV_POLL_SLEEP); }
-#ifndef LV_XCD_ST_MODS
-#define LV_XCD_ST_MODS ""                   // measurement knob: cache-policy bits of the XCD-local granule store (" nt", " sc0", ...)
-#endif
 __device__ __forceinline__ void lv_xcd_store_q4(void* p, uint4 v) {
     const lv_u32x4v d = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off" LV_XCD_ST_MODS "\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
 }
 // DPP row_shr with a bank mask (v_mov_b32_dpp row_shr:SHIFT bank_mask:1 << BANK): lanes of bank BANK (lanes 4 BANK .. 4 BANK + 3 of
 // every 16-lane row) take src from the lane SHIFT positions lower in their row, every other lane keeps old.  Merges the valid

@@ -18,9 +18,6 @@
 // loads 16 B (eight adjacent rows at one k) for 4 consecutive k and transposes the 8x4 block in registers (16 integer
 // ops) into the eight rows' k-quads; row e of octet m8 is kept in LDS row 16*e + m8 so that the lanes of one store hit
 // consecutive LDS rows, and the epilogue undoes that permutation for free in its row index.
-#ifndef LV_B16_T256_DMA
-#define LV_B16_T256_DMA 1
-#endif
 #if defined(LV_TRACE)
 #define lv_trace_buf lv_trace_buf_gemm      // (one trace pointer per translation unit: device code is not relocatable)
 #endif
@@ -311,22 +308,8 @@ __global__ __launch_bounds__(256) void lv_gemm_b16_kernel(GemmQ p) {
         }
 }
 
-#ifndef LV_B16_PP_DMA
-#define LV_B16_PP_DMA 0        // ping-pong schedule: units of the next tile's DMA per LOAD segment of k-steps 0..3: 0 = 2,2,0,0; 1 = 2,1,1,0; 2 = 1,1,1,1
-#endif
 #ifndef LV_B16_PP_ABL
 #define LV_B16_PP_ABL 0        // ablation switches for profiles/microbench only (results are wrong): 1 = no DMA in the loop, 2 = no MFMA, 4 = no fragment reads, 8 = no barriers, 16 = a second tile's DMA stays in flight (vmcnt(8)), 32 = only the A tile is staged, 64 = every workgroup stages tile (0, 0), 128 = no source-side swizzle
-#endif
-#ifndef LV_B16_PP_WAIT
-#define LV_B16_PP_WAIT 1       // ping-pong schedule: group 0 waits for its DMA at the end of the MFMA segment of k-step 3 (0: both groups at the end of the LOAD segment)
-#endif
-#ifndef LV_B16_PP_PRIO
-#define LV_B16_PP_PRIO 1       // ping-pong schedule: s_setprio 1 around the MFMA segment
-#endif
-#ifndef LV_B16_T256_ORDER
-#define LV_B16_T256_ORDER 1   // 256 x 256 kernel: fragments of k-step ks+1 requested before (0) / in the middle of (1) the MFMAs of k-step ks
-                              // (1 since the DMA moved into the first half of the tile: logits 310 -> 298 us, dO 304 -> 295, fused NLL 325 -> 317;
-                              //  DMA ahead of the fragment reads, or one unit behind each MFMA group, measured the same)
 #endif
 #ifndef LV_B16_SINGLE_WAVES
 #define LV_B16_SINGLE_WAVES 4   // single-buffer 128 x 128 kernel: waves per SIMD its register budget is cut to (0 = unconstrained: 161 registers, 3 workgroups per CU; 4: 123-128 registers, 4 per CU -- the 1600-tile input projection then needs two rounds instead of three: 47-53 -> 43 us)
@@ -1049,9 +1032,10 @@ __global__ __launch_bounds__(512) void lv_gemm_b16_t256_kernel(GemmQ p, Tail256 
         }
     };
     // One K tile (Ac, Bc) while the next one (kt_next) streams into (Ad, Bd).  Pinned with scheduling barriers: the fragments of
-    // k-step ks + 1 are requested BEFORE the 8 MFMAs of k-step ks (left alone the compiler reads each fragment group right before
-    // its MFMAs and waits out the LDS latency eight times per tile), and the tile's 8 DMA instructions go out two per k-step BETWEEN
-    // the MFMAs (an LDS-DMA instruction costs 60-180 issue cycles; at the top of the tile they would all run with the pipe empty).
+    // k-step ks + 1 are requested between the two MFMA groups of k-step ks (left alone the compiler reads each fragment group right
+    // before its MFMAs and waits out the LDS latency eight times per tile), and the tile's 8 DMA instructions go out BETWEEN the MFMAs
+    // of its first two k-steps (an LDS-DMA instruction costs 60-180 issue cycles; at the top of the tile they would all run with the
+    // pipe empty).
     LV_TRACE_ONLY(int tr_kt = 0;)
     auto mma_tile = [&](auto staging, LdsTile2& Ac, LdsTile2& Bc, int kt_next, LdsTile2& Ad, LdsTile2& Bd) {
         constexpr bool STAGE = decltype(staging)::value;
@@ -1064,22 +1048,14 @@ __global__ __launch_bounds__(512) void lv_gemm_b16_t256_kernel(GemmQ p, Tail256 
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
             const int cur = ks & 1, nxt = cur ^ 1;
-#if LV_B16_T256_ORDER == 0
-            if (ks + 1 < BK / 16) {
-                const int c = 2 * (ks + 1) + lh;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) fb[nxt][j] = Bc[brow + 32 * j][c ^ sx];
-#pragma unroll
-                for (int i2 = 0; i2 < 4; ++i2) fa[nxt][i2] = a_frag(Ac, ks + 1, i2);
-            }
-            LV_SCHED_BARRIER();
-#endif
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) acc[i][j] = lv_mfma_32x32x16_bf16(fa[cur][i], fb[cur][j], acc[i][j]);
             LV_SCHED_BARRIER();
-#if LV_B16_T256_ORDER == 1
+            // (in the MIDDLE of the k-step's MFMAs since the DMA moved into the first half of the tile -- against requesting them in
+            //  front of the MFMAs: logits 310 -> 298 us, dO 304 -> 295, fused NLL 325 -> 317; DMA ahead of the fragment reads, or one
+            //  unit behind each MFMA group, measured the same)
             if (ks + 1 < BK / 16) {
                 const int c = 2 * (ks + 1) + lh;
 #pragma unroll
@@ -1087,27 +1063,16 @@ __global__ __launch_bounds__(512) void lv_gemm_b16_t256_kernel(GemmQ p, Tail256 
 #pragma unroll
                 for (int i2 = 0; i2 < 4; ++i2) fa[nxt][i2] = a_frag(Ac, ks + 1, i2);
             }
-#endif
             // the next tile's 8 DMA instructions: two UNITS (4 instructions) behind each of the first two k-steps' first MFMA groups, so
             // that the last of them has half a tile of MFMAs to land under (one unit per k-step left the last pair ~600 cycles short
             // at the end-of-tile vmcnt(0): 8192^3 1090 -> 1185 TF, dW_pred 290 -> 276 us, dO 307 -> 300; all four units at the top, or
-            // 1-2-1, measured worse: profiles/microbench/gemm_b16_shapes.py with -DLV_B16_T256_DMA=0/2/3/4)
-#if LV_B16_T256_DMA == 1
+            // 2-1-1, 3-1 and 1-2-1 measured worse: docs/HISTORY.md)
             if constexpr (STAGE) {
                 if (ks < 2) {
 #pragma unroll
                     for (int i = 0; i < UN / 2; ++i) stage_unit(kt_next, (UN / 2) * ks + i, Ad, Bd);
                 }
             }
-#elif LV_B16_T256_DMA == 2
-            if constexpr (STAGE) { if (ks == 0) { stage_unit(kt_next, 0, Ad, Bd); stage_unit(kt_next, 1, Ad, Bd); } else if (ks < 3) stage_unit(kt_next, ks + 1, Ad, Bd); }
-#elif LV_B16_T256_DMA == 3
-            if constexpr (STAGE) { if (ks == 0) { stage_unit(kt_next, 0, Ad, Bd); stage_unit(kt_next, 1, Ad, Bd); stage_unit(kt_next, 2, Ad, Bd); } else if (ks == 1) stage_unit(kt_next, 3, Ad, Bd); }
-#elif LV_B16_T256_DMA == 4
-            if constexpr (STAGE) { if (ks == 0) stage_unit(kt_next, 0, Ad, Bd); else if (ks == 1) { stage_unit(kt_next, 1, Ad, Bd); stage_unit(kt_next, 2, Ad, Bd); } else if (ks == 2) stage_unit(kt_next, 3, Ad, Bd); }
-#else
-            if constexpr (STAGE) stage_unit(kt_next, ks, Ad, Bd);
-#endif
             LV_SCHED_BARRIER();
 #pragma unroll
             for (int i = 2; i < 4; ++i)
@@ -1155,31 +1120,25 @@ __global__ __launch_bounds__(512) void lv_gemm_b16_t256_kernel(GemmQ p, Tail256 
                 for (int i2 = 0; i2 < 4; ++i2) fa[i2] = a_frag(Ac, ks, i2);
 #endif
                 LV_SCHED_BARRIER();
-#if LV_B16_PP_ABL & 1
-#elif LV_B16_PP_DMA == 0
-                if (ks < 2) {
+#if !(LV_B16_PP_ABL & 1)
+                if (ks < 2) {           // the next tile's DMA: two units in each of the LOAD segments of k-steps 0 and 1
 #pragma unroll
                     for (int i = 0; i < UN / 2; ++i) stage_unit(kt_next, (UN / 2) * ks + i, Ad, Bd);
                 }
-#elif LV_B16_PP_DMA == 1
-                if (ks == 0) { stage_unit(kt_next, 0, Ad, Bd); stage_unit(kt_next, 1, Ad, Bd); }
-                else if (ks < 3) stage_unit(kt_next, ks + 1, Ad, Bd);
-#else
-                stage_unit(kt_next, ks, Ad, Bd);
 #endif
                 LV_SCHED_BARRIER();
 #if LV_B16_PP_ABL & 16
                 if (ks == BK / 16 - 1) LV_WAIT_VMEM_N(8);
 #else
                 // the DMA wait: every wave before the SAME barrier -- the one behind which group 0 starts reading the next tile --, i.e.
-                // group 1 at the end of this LOAD segment, group 0 one segment later, at the end of its MFMA segment (LV_B16_PP_WAIT 1)
-                if (ks == BK / 16 - 1 && (!LV_B16_PP_WAIT || wm == 1)) LV_WAIT_VMEM();
+                // group 1 at the end of this LOAD segment, group 0 one segment later, at the end of its MFMA segment
+                if (ks == BK / 16 - 1 && wm == 1) LV_WAIT_VMEM();
 #endif
                 LV_WAIT_LDS();
                 if (!(LV_B16_PP_ABL & 8)) LV_S_BARRIER();
                 LV_SCHED_BARRIER();
                 // MFMA segment
-                if (LV_B16_PP_PRIO) LV_SETPRIO(1);
+                LV_SETPRIO(1);
 #if LV_B16_PP_ABL & 2
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -1191,9 +1150,9 @@ __global__ __launch_bounds__(512) void lv_gemm_b16_t256_kernel(GemmQ p, Tail256 
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) acc[i][j] = lv_mfma_32x32x16_bf16(fa[i], fb[j], acc[i][j]);
 #endif
-                if (LV_B16_PP_PRIO) LV_SETPRIO(0);
+                LV_SETPRIO(0);
                 LV_SCHED_BARRIER();
-                if (LV_B16_PP_WAIT && ks == BK / 16 - 1 && wm == 0) LV_WAIT_VMEM();
+                if (ks == BK / 16 - 1 && wm == 0) LV_WAIT_VMEM();
                 if (!(LV_B16_PP_ABL & 8)) LV_S_BARRIER();
                 LV_SCHED_BARRIER();
             }

@@ -6,9 +6,9 @@
 // rows).  Decomposition and hand-off: a group = the 32 workgroups with the same blockIdx % 8; a group owns a slice of the batch
 // and carries it through all T steps, groups never talk; W_hh stays register-resident for the whole call (a wave's 64 KB slice
 // in 256 AGPRs); per timestep the only exchange is h_t (forward, all-gather) or partial dh sums (BPTT, reduce-scatter) inside
-// the group, as tagged granules gathered by polling; bulk I/O in blocks of timesteps; all spins bounded.  Since the end of round 6 a
-// granule is 16 bytes and every dword of it carries its own tag (LV_FWD_Q / LV_RS_Q below; the 8-byte granules with one tag per
-// granule remain as the A/B builds): the hand-off is bound by the NUMBER of load / store instructions, not by their bytes, and
+// the group, as tagged granules gathered by polling; bulk I/O in blocks of timesteps; all spins bounded.  A granule is 16 bytes --
+// four units of one batch row -- and every dword of it carries its own tag: the hand-off is bound by the NUMBER of load / store
+// instructions, not by their bytes (the 8-byte granules with one tag per granule that came first: docs/HISTORY.md), and
 // 16-byte atomicity is assumed nowhere (the CI emulator tears the stores).  The contraction:
 //
 //   * v_mfma_f32_16x16x32_bf16 with the operands SWAPPED: the weights are the A operand (16 gate columns / output units as the
@@ -16,7 +16,7 @@
 //     (64 MFMAs x 16 cycles per wave and timestep) for up to 16 rows, and the D tile comes out as [gate column][batch row]: a
 //     lane holds FOUR CONSECUTIVE gate columns of ONE batch row -- in the forward's unit-major column order exactly the
 //     (i, f, g, o) of one unit, so the K-split partial products cross the workgroup as float4 records, and in the BPTT four
-//     consecutive hidden units of one row, i.e. two ready-made partial-sum granules.
+//     consecutive hidden units of one row, i.e. one ready-made partial-sum granule.
 //   * forward (K-split): wave w gathers K-quarter w of h_{t-1} (rows x 64 granules of four units), 8 fragment
 //     reads + 64 MFMAs, 8 float4 LDS writes, ONE barrier, every (row, unit) thread adds the four quarters and runs the cell.
 //   * BPTT (reduce-scatter): a workgroup receives 32 senders x rows x 8 granules (four partial sums each) of partial dh
@@ -38,32 +38,17 @@ __device__ unsigned long long* lv_trace_buf = nullptr;
 extern "C" int lv_trace_set(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(lv_trace_buf), &p, sizeof(p)); }
 #endif
 
-#ifndef LV_SBB16
-#define LV_SBB16 8                      // (measurement knobs of profiles/microbench: input block length of the 16-row BPTT,
-#endif                                  //  I/O block length and granules per lane and polling round of the 16-row forward)
-#ifndef LV_HB16
-#define LV_HB16 2                       // slot batches of the BPTT receive polled together (2: two rounds at 16 rows; 4: one)
-#endif
-#ifndef LV_SBK16
-#define LV_SBK16 4
-#endif
-#ifndef LV_GJ16
-#define LV_GJ16 16
-#endif
-#ifndef LV_FWD_Q
-#define LV_FWD_Q 2                      // forward: h travels as 16-byte granules (four units, each dword = binary16 / bf16 bits under a 16-bit
-#endif                                  // tag of its own): 2 = every instantiation, 1 = the 4-row one only, 0: 8-byte granules (A/B builds)
 #ifndef LV_RS_Q
-#define LV_RS_Q 2                       // BPTT: the reduce-scatter's partial sums travel as 16-byte granules (rs4_*: four 30-bit floats, 2 tag
-#endif                                  // bits each): 2 = every instantiation, 1 = the 4-row one only, 0: 8-byte granules (A/B builds)
+#define LV_RS_Q 2                       // BPTT: 2 = the shipped 16-byte granules in every instantiation; 1 = in the 4-row one only, 0: the
+#endif                                  // 8-byte granules that came first.  The forward has no such switch any more; this one stays because
+                                        // deleting the 8-byte arms, though the product build never runs them, changes the register
+                                        // allocation of every BPTT instantiation (see the BPTT block comment)
 #ifndef LV_P16_ABL
 #define LV_P16_ABL 0                    // measurement knob (profiles/microbench/lstm_anatomy_probe.py): WHAT-IF builds of the final
 #endif                                  // kernels with one phase of a timestep removed -- results are garbage, the time is the point.
                                         // bit 0: no MFMAs; bit 1: hand-off tags not tested (no step waits for its producers: the
                                         // local pipeline alone); bit 2: no transcendental cell / gate-gradient math; bit 3: no
-                                        // LDS quarter-sum exchange + barrier (forward) / dG image barrier (BPTT); bit 4 (forward): the
-                                        // gathered granules are not staged through LDS (fragments straight from the poll registers);
-                                        // bit 5 (forward): the granules are not loaded at all (bits 4, 5: builds with LV_FWD_Q = 0 only)
+                                        // LDS quarter-sum exchange + barrier (forward) / dG image barrier (BPTT)
 
 namespace {
 
@@ -75,7 +60,7 @@ constexpr int HP16 = PH / 2 + 8;        // dwords per row of the gathered h imag
 constexpr int DP16 = 64 + 8;            // dwords per row of the dG image (18 slots)
 constexpr int RED_SLOTS = 33;           // float4 slots per row of a quarter product (32 units + 1: 8 consecutive rows = 8 slot classes)
 constexpr int SAVED_PER_ROW = 160;     // floats per batch row in a (workgroup, timestep) record of the saved activations: 32 units x (4 gates + c)
-constexpr int RS16_SLOTS_MAX = 256;     // granule slots of one (receiver, sender) pair at 16 rows (16 RP in general: the pairs are dense)
+constexpr int RS16_SLOTS_MAX = 256;     // 8-byte units (gran_t) of one (receiver, sender) pair at 16 rows (16 RP in general: the pairs are dense)
 template <int V> struct lv_const { static constexpr int value = V; };
 
 // ---- weight images ------------------------------------------------------------------------------------------------------------
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(256) void pack_w_rs16_kernel(const float* __restric
 struct Fwd16P {
     const float* gx; const uint4* wpk;
     float* hs; float* cs; float* saved;
-    gran_t* hx;                 // exchange: [2 parity][8 groups][16 rows][H/2] granules, zeroed before the launch
+    gran_t* hx;                 // exchange: [2 parity][8 groups][16 rows][H/4 granules of 16 bytes], zeroed before the launch
     int* status;
     int T, B, R;
     uint4* clr; long clr_n;     // double-buffered exchange (flags bit 1): the OTHER half, zeroed by this launch for the next one (clr_n uint4s)
@@ -155,19 +140,20 @@ __device__ __forceinline__ void clear_other_half(uint4* q, long n) {
 
 // =====================================================================================================================
 // forward.  RP: rows per group this instantiation carries (4 / 8 / 16); NP = pairs (row, unit) per thread; SBK = timesteps per
-// I/O block; GJ = granules per lane in flight per polling round.
+// I/O block (the block registers exist once per pair: 4 at 16 rows; the other lengths that were measured were slower or
+// spilled, docs/HISTORY.md).
 template <int RP> struct Cfg16 {
     static constexpr int NP = RP > 8 ? 2 : 1;
-    static constexpr int SBK = RP > 8 ? LV_SBK16 : 8;
-    static constexpr int SBB = RP > 8 ? LV_SBB16 : 8; // BPTT: timesteps per input block
-    static constexpr int GJ = RP > 8 ? LV_GJ16 : (RP > 4 ? 16 : 8);
+    static constexpr int SBK = RP > 8 ? 4 : 8;
+    static constexpr int SBB = 8;                     // BPTT: timesteps per input block
 };
 
 template <int RP>
 struct __attribute__((aligned(16))) Fwd16Lds {
     uint32_t hl[RP * HP16];                   // gathered h_{t-1}: [row][k/2]; wave w owns dwords [128w, 128w + 128) of every row
     f32x4 red[2][4][RP][RED_SLOTS];           // [step parity][wave]: quarter product, (i, f, g, o) of [row][unit of the workgroup]
-    uint32_t dump[256];                       // where the lanes of a ragged gather round put what they did not need (no branch per granule)
+    uint32_t dump[256];                       // unused since the 8-byte gather left; kept: it places `abort` and the XIN members behind
+                                              // it, and without it the kernels' LDS size and offsets -- their device code -- change
     int abort;
 };
 
@@ -179,10 +165,7 @@ struct __attribute__((aligned(16))) Fwd16Lds {
 // reads back only what it wrote: linear ds_read_b128) and the others in VGPRs.
 constexpr int XNI = 512;                // input width the XIN forward is built for
 constexpr int XKS = XNI / 32;           // k-steps of the mini-product
-#ifndef LV_XIN_KS_LDS
-#define LV_XIN_KS_LDS 12                // k-steps of the W_ih slice kept in LDS (96 KB); the other 4 sit in 32 VGPRs per lane
-#endif
-constexpr int XKL = LV_XIN_KS_LDS;
+constexpr int XKL = 12;                 // k-steps of the W_ih slice kept in LDS (96 KB); the other 4 sit in 32 VGPRs per lane
 constexpr int XS_PITCH = XNI / 8 + 2;   // 16-byte slots per column of the staged input rows (66: = 2 mod 16)
 struct __attribute__((aligned(16))) Fwd16XLds : Fwd16Lds<4> {
     uint4 wih[4][XKL][2][64];           // [wave][ks][column block 2w + j][lane]: A fragments of the wave's 32 gate columns
@@ -195,14 +178,13 @@ template <class A, class B> struct lv_pick_t<false, A, B> { typedef B type; };
 template <int RP, bool LOCAL, bool F16 = false, bool XIN = false>
 __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
     static_assert(!XIN || RP == 4, "the fused input projection maps the tile's 16 columns to 4 steps x 4 rows");
-    // LOCAL: hand-off stores without the agent-scope write-through (lv_xcd_store_u64): valid while a group's 32 workgroups share an XCD
+    // LOCAL: hand-off stores without the agent-scope write-through (lv_xcd_store_q4): valid while a group's 32 workgroups share an XCD
     // F16: the recurrent operands -- the register image of W_hh and the h granules -- are IEEE binary16 and the products run on
     // v_mfma_f32_16x16x32_f16: the same kernel at 11 instead of 8 bits of significand for the WEIGHTS, whose rounding acts at every
     // timestep alike (the encoder's forward: 1.4e-4 -> 2e-5 relative on the KL, profiles/r05a_kl_ablation.txt); h in (-1, 1) and
     // LSTM weights are far inside binary16's range.  The BPTT keeps bf16 (gradients need the exponent range).
     auto h16 = [](float v) -> uint32_t { return F16 ? (uint32_t)lv_f32_to_f16_bits(v) : lv_f32_to_bf16_bits(v); };
-    auto put = [](gran_t* q, gran_t v) { if (LOCAL) lv_xcd_store_u64(q, v); else gran_store(q, v); };
-    constexpr int NP = Cfg16<RP>::NP, SBK = Cfg16<RP>::SBK, GJ = Cfg16<RP>::GJ;
+    constexpr int NP = Cfg16<RP>::NP, SBK = Cfg16<RP>::SBK;
     typedef typename lv_pick_t<XIN, Fwd16XLds, Fwd16Lds<RP>>::type Lds;
     LV_BLOCK_SHARED(Lds, sm);
     int& s_abort = sm.abort;
@@ -257,12 +239,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
     }
     gran_t* const hx_g = p.hx + (long)group * 16 * (PH / 2);
     const long hx_par = (long)PGROUPS * 16 * (PH / 2);
-    const bool even = !(uw & 1);
 
-    // QF: a granule is 16 bytes = the four units 4i .. 4i + 3 of a row, every dword its unit's 16 bits under the low 16 bits of
-    // the state's tag -- a granule is valid when all four dwords carry it, so 16-byte atomicity is assumed nowhere.  Half as many load
-    // instructions per poll for the same bytes; the publishing lane of a quad collects its neighbours' dwords by DPP.
-    constexpr bool QF = LV_FWD_Q == 2 || (RP == 4 && LV_FWD_Q == 1);
+    // A granule is 16 bytes = the four units 4i .. 4i + 3 of a row, every dword its unit's 16 bits under the low 16 bits of
+    // the state's tag -- a granule is valid when all four dwords carry it, so 16-byte atomicity is assumed nowhere.  The publishing
+    // lane of a quad collects its neighbours' dwords by DPP.
     auto tagq = [](int state) -> uint32_t { return 1u + (uint32_t)state % 0xFFFFu; };
     auto publish_q = [&](int state, int q, float hval) {
         const uint32_t dw = h16(hval) | (tagq(state) << 16);
@@ -273,12 +253,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
         }
     };
 #pragma unroll
-    for (int q = 0; q < NP; ++q) {      // publish the initial state hs[0] as state 0 (tag 1)
-        if constexpr (QF) { publish_q(0, q, own[q] ? p.hs[pidx[q]] : 0.f); continue; }
-        const uint32_t mine = h16(own[q] ? p.hs[pidx[q]] : 0.f);
-        const uint32_t next = lv_lane_xor1_u32(mine);      // (even lanes: their right-hand neighbour; DPP, no LDS round trip)
-        if (own[q] && even) put(hx_g + (long)prow[q] * (PH / 2) + (punit >> 1), ((gran_t)1u << 32) | (gran_t)(mine | (next << 16)));
-    }
+    for (int q = 0; q < NP; ++q) publish_q(0, q, own[q] ? p.hs[pidx[q]] : 0.f);      // the initial state hs[0] as state 0 (tag 1)
 
     float4 gxb[XIN ? 1 : NP][XIN ? 1 : SBK];
     f32x4 addv[NP];                                           // XIN: the projection's addend of the pair, constant over t
@@ -385,9 +360,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
     __syncthreads();
     x_product(0);                                              // (its readers wait at the barrier of step 0)
 
-    const int nq = rows * 128;                                 // granules of this wave's K quarter
     const int brow = (l & 15) < rows ? (l & 15) : 0;           // batch row of this lane's B fragments (rows beyond the slice re-read row 0)
-    uint32_t abl_keep[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // (LV_P16_ABL bit 4 only)
     for (int tb = 0; tb < T; tb += SBK) {
 #pragma unroll
         for (int s2 = 0; s2 < SBK; ++s2) {
@@ -395,81 +368,44 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
             if (t >= T) break;
             LV_TRACE_MARK(t, 0);
             // ---- gather K-quarter w of state t (tag t + 1) into this wave's part of the LDS image ---------------------------
-            const gran_t* src = hx_g + (long)(t & 1) * hx_par + 128 * w;
-            const uint32_t want = (uint32_t)(t + 1);
-            if constexpr (QF) {
-                // lane l takes granule 64w + l (k = 256w + 4l .. + 3) of each of the slice's rows -- every load instruction reads 1 KB
-                // of one row -- in polling rounds of 4 (4-row instantiation) or 8 rows; rows the slice does not have are neither tested
-                // nor staged
-                constexpr int QR = RP == 4 ? 4 : 8;
-                const char* sq = reinterpret_cast<const char*>(hx_g + (long)(t & 1) * hx_par) + (64 * w + l) * 16;
-                const long rowb = (long)(PH / 2) * 8;
-                const uint32_t wq = tagq(t) << 16;
-                auto round = [&](auto R0) {      // (a lambda per round: a loop over rounds around the polling loop is not unrolled)
-                    constexpr int r0 = decltype(R0)::value;
-                    if (r0 >= rows) return;
-                    uint4 v[QR];
-                    int spins = 0;
-                    bool ok;
-                    do {
-                        if constexpr (QR == 4)
-                            lv_agent_load_q4x4(sq, sq + (rows > 1 ? rowb : 0), sq + (rows > 2 ? 2 * rowb : 0), sq + (rows > 3 ? 3 * rowb : 0), v);
-                        else {
-                            // (rows the slice does not have are loaded from their own -- allocated, unused -- rows of the exchange)
-                            static_assert((PH / 2) * 8 == 4096, "lv_agent_load_q4x8_rows: rows 4 KB apart");
-                            lv_agent_load_q4x8_rows(sq + r0 * rowb, reinterpret_cast<uint4 (&)[8]>(v));
-                        }
-                        uint32_t x = 0u;
-#pragma unroll
-                        for (int j = 0; j < QR; ++j)
-                            if (r0 + j < rows) x |= (v[j].x ^ wq) | (v[j].y ^ wq) | (v[j].z ^ wq) | (v[j].w ^ wq);
-                        ok = (LV_P16_ABL & 2) ? true : (x >> 16) == 0u;
-                        ok = __all(ok);
-                        if (!ok && ++spins > SPIN_LIMIT) { s_abort = 1; break; }
-                        if (!ok) lv_poll_backoff();
-                    } while (!ok);
-                    LV_TRACE_VAL(t, 6, spins);
-#pragma unroll
-                    for (int j = 0; j < QR; ++j)
-                        if (r0 + j < rows)
-                            *reinterpret_cast<uint2*>(&sm.hl[(r0 + j) * HP16 + 128 * w + 2 * l]) =
-                                make_uint2((v[j].x & 0xFFFFu) | (v[j].y << 16), (v[j].z & 0xFFFFu) | (v[j].w << 16));
-                };
-                round(lv_const<0>());
-                if constexpr (RP > QR) round(lv_const<QR>());
-            } else
-            for (int base = 0; base < nq; base += 64 * GJ) {
-                // every poll round issues ALL its loads before it looks at a tag (first build: a load and its tag test per granule
-                // inside one predicated block compiled to load -> wait -> compare, GJ dependent round trips: 6.8 us per step at 8 rows)
-                gran_t v[GJ];
+            // lane l takes granule 64w + l (k = 256w + 4l .. + 3) of each of the slice's rows -- every load instruction reads 1 KB
+            // of one row -- in polling rounds of 4 (4-row instantiation) or 8 rows; rows the slice does not have are neither tested
+            // nor staged
+            constexpr int QR = RP == 4 ? 4 : 8;
+            const char* sq = reinterpret_cast<const char*>(hx_g + (long)(t & 1) * hx_par) + (64 * w + l) * 16;
+            const long rowb = (long)(PH / 2) * 8;
+            const uint32_t wq = tagq(t) << 16;
+            auto round = [&](auto R0) {      // (a lambda per round: a loop over rounds around the polling loop is not unrolled)
+                constexpr int r0 = decltype(R0)::value;
+                if (r0 >= rows) return;
+                uint4 v[QR];
                 int spins = 0;
                 bool ok;
                 do {
-                    ok = true;
-#pragma unroll
-                    for (int j = 0; j < GJ; ++j) {
-                        const int q = base + j * 64 + l;
-                        const bool in = q < nq;
-                        if constexpr (LV_P16_ABL & 32) { v[j] = ((gran_t)want << 32) | (gran_t)(uint32_t)(q + t); continue; }
-                        v[j] = gran_load(src + (in ? (q >> 7) * (PH / 2) + (q & 127) : 0));      // out-of-range lanes re-read granule 0: no branch
-                        if (!(LV_P16_ABL & 2)) ok = ok && (!in || (uint32_t)(v[j] >> 32) == want);
+                    if constexpr (QR == 4)
+                        lv_agent_load_q4x4(sq, sq + (rows > 1 ? rowb : 0), sq + (rows > 2 ? 2 * rowb : 0), sq + (rows > 3 ? 3 * rowb : 0), v);
+                    else {
+                        // (rows the slice does not have are loaded from their own -- allocated, unused -- rows of the exchange)
+                        static_assert((PH / 2) * 8 == 4096, "lv_agent_load_q4x8_rows: rows 4 KB apart");
+                        lv_agent_load_q4x8_rows(sq + r0 * rowb, reinterpret_cast<uint4 (&)[8]>(v));
                     }
+                    uint32_t x = 0u;
+#pragma unroll
+                    for (int j = 0; j < QR; ++j)
+                        if (r0 + j < rows) x |= (v[j].x ^ wq) | (v[j].y ^ wq) | (v[j].z ^ wq) | (v[j].w ^ wq);
+                    ok = (LV_P16_ABL & 2) ? true : (x >> 16) == 0u;
                     ok = __all(ok);
                     if (!ok && ++spins > SPIN_LIMIT) { s_abort = 1; break; }
                 } while (!ok);
                 LV_TRACE_VAL(t, 6, spins);
-                if constexpr (LV_P16_ABL & 16) {
 #pragma unroll
-                    for (int j = 0; j < GJ; ++j) abl_keep[j & 7] ^= (uint32_t)v[j];
-                } else {
-#pragma unroll
-                for (int j = 0; j < GJ; ++j) {
-                    const int q = base + j * 64 + l;
-                    uint32_t* dstw = q < nq ? &sm.hl[(q >> 7) * HP16 + 128 * w + (q & 127)] : &sm.dump[tid];
-                    *dstw = (uint32_t)v[j];
-                }
-                }
-            }
+                for (int j = 0; j < QR; ++j)
+                    if (r0 + j < rows)
+                        *reinterpret_cast<uint2*>(&sm.hl[(r0 + j) * HP16 + 128 * w + 2 * l]) =
+                            make_uint2((v[j].x & 0xFFFFu) | (v[j].y << 16), (v[j].z & 0xFFFFu) | (v[j].w << 16));
+            };
+            round(lv_const<0>());
+            if constexpr (RP > QR) round(lv_const<QR>());
             // Bulk I/O goes out right BEHIND a completed gather: a wave's loads and stores retire in order, so whatever is issued in
             // front of a poll is waited for by that poll with its full memory latency (first build: everything at the block
             // boundary).  First step of a block: the previous block's results and the one gx slot that was still in use; last
@@ -486,14 +422,9 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
             f32x4 acc[8];
             const uint4* bp = reinterpret_cast<const uint4*>(sm.hl + brow * HP16 + 128 * w) + kq;
             uint4 bfr[8];
-            if constexpr (LV_P16_ABL & 16) {
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) bfr[ks] = make_uint4(abl_keep[ks], abl_keep[(ks + 1) & 7], abl_keep[(ks + 2) & 7], abl_keep[(ks + 3) & 7]);
-            } else {
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) bfr[ks] = bp[ks * 4];
-            }
-            LV_SCHED_BARRIER();                                // all eight fragment reads in flight before the first MFMA (left alone the
+            LV_SCHED_BARRIER();                               // all eight fragment reads in flight before the first MFMA (left alone the
                                                                // compiler reads each one right before its eight MFMAs, behind lgkmcnt(0))
             if constexpr (LV_P16_ABL & 1) {
 #pragma unroll
@@ -549,12 +480,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
                     recb[q][s2] = f32x4{ig, fg, gg, og};
                     cb[q][s2] = c; hb[q][s2] = h;
                 }
-                if constexpr (QF) { publish_q(t + 1, q, h); continue; }
-                const uint32_t mine = h16(h);
-                const uint32_t next = lv_lane_xor1_u32(mine);      // (even lanes: their right-hand neighbour; DPP, no LDS round trip)
-                if (own[q] && even)
-                    put(hx_g + (long)((t + 1) & 1) * hx_par + (long)prow[q] * (PH / 2) + (punit >> 1),
-                        ((gran_t)(uint32_t)(t + 2) << 32) | (gran_t)(mine | (next << 16)));
+                publish_q(t + 1, q, h);
             }
             if ((s2 & 3) == 3) x_product(((t + 1) >> 2) & 1);
             LV_TRACE_MARK(t, 5);
@@ -564,17 +490,23 @@ __global__ __launch_bounds__(256) void lstm_fwd_persist_k16_kernel(Fwd16P p) {
 }
 
 // =====================================================================================================================
-// BPTT, reduce-scatter hand-off.  Exchange buffer: [parity][group][receiver (32)][sender (32)][16 RP granules], DENSE for the
-// instantiation (a first layout with a fixed 2 KB stride per pair used 512 B of every 2 KB at 4 rows and 7 us per timestep: a
-// quarter of the L2 channels carried all the traffic).  A sender lane holds, for batch row c and column block nb, the partial dh of
-// units u = 16 b + 4 rq + 2 h2 + {0, 1} of receiver 8w + (nb >> 1) (b = nb & 1; rq = l >> 4; h2 = the register pair): slot
-// s = (2 b + h2) 4 RP + 4 c + rq, so that ONE store instruction (fixed b, h2) writes one contiguous run of 32 RP bytes -- whole
-// 128-byte lines, not four partial writes per line.  A receiver wave w sums the slots [4 RP w, 4 RP w + 4 RP) (b = w >> 1,
-// h2 = w & 1) in batches of 16 (batch beta: rows 4 beta + (p >> 2), rq = p & 3 for lane position p = l & 15): lane group l >> 4 =
-// eight of the 32 senders, two shuffles add the four groups.  Owners: lanes 0..31 take batch 2q, lanes 32..63 batch 2q + 1
-// (q = pair index), low / high half of the granule by (l >> 4) & 1.
-// (That is the 8-BYTE granule form, LV_RS_Q = 0, kept for A/B builds.  The shipped form moves the same bytes of the same dense
-//  per-pair extent as 16-byte granules of four units each -- layout, lane maps and the transposing sum: the QB comments in the kernel.)
+// BPTT, reduce-scatter hand-off.  Exchange buffer: [parity][group][receiver (32)][sender (32)][8 RP granules of 16 bytes], DENSE
+// for the instantiation (a first layout with a fixed 2 KB stride per pair used 512 B of every 2 KB at 4 rows and 7 us per
+// timestep: a quarter of the L2 channels carried all the traffic).  A granule holds the partial dh of FOUR consecutive units of one
+// batch row (rs4_*: 30-bit floats, each under a 2-bit phase tag of its own); granule (unit block b, row c, unit quad rq) of a pair
+// lies at (b RP + c) 4 + rq.  A sender lane (c = l & 15, rq = l >> 4) holds, for column block nb, exactly such a quad -- units
+// 16 b + 4 rq + 0..3 (b = nb & 1) of receiver 8w + (nb >> 1) -- so one store instruction writes one contiguous run of 64 RP bytes.
+// A receiver wave w takes the 2 RP granules from 2 RP w on in ROUNDS of eight (lane l: granule l & 7 of the round, senders
+// 4 (l >> 3) + 0..3), sums the senders in a fixed order and ends in a transposing butterfly that leaves every lane with the total of
+// ONE unit: unit 2 ((l >> 4) & 1) + (l >> 5) of its quad l & 3.  4 rows: one round, the lanes with bit 3 clear own (row
+// 2 (w & 1) + ((l >> 2) & 1)); 8 / 16 rows: pair q of a lane comes from round 2q + ((l >> 3) & 1), row
+// (RP / 2)(w & 1) + 4q + 2 ((l >> 3) & 1) + ((l >> 2) & 1), and every lane owns.
+// The 8-byte granules of two units under one tag that came first (docs/HISTORY.md) are still in the kernel, behind LV_RS_Q = 0: the
+// non-QB arms of uw / prow / own, rx / tx / tx4, receive_round and the `put` stores, over the same dense extent (slot
+// s = (2 b + h2) 4 RP + 4 c + rq for unit pair h2 of a quad).  Nothing in the product build runs them, but they are not dead to the
+// compiler: their address terms share subexpressions with the live ones, and deleting them changes how the lane arithmetic of
+// every BPTT instantiation is formed and which registers it gets -- device code that is not bit-identical has to be measured again
+// before it ships, so they go in a change that does that.
 struct Bwd16P {
     const float* dh_ext; const float* dh_last;
     const uint4* wpk;
@@ -711,7 +643,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
     // Two batch rows (16 granules per lane) are polled at a time: all 32 granules of the 16-row form in flight at once would
     // need 64 registers next to the 256 of the weights (the first build spilled 92); the sums over the senders are taken in a
     // fixed order once a round is complete, so the result does not depend on arrival order.
-    constexpr int HB = NB < LV_HB16 ? NB : LV_HB16;
+    constexpr int HB = NB < 2 ? NB : 2;
     LV_TRACE_ONLY(int tr_spins[2] = {0, 0};)
     auto receive_round = [&](auto H0, const gran_t* src, uint32_t want, float (&dh_rec)[NP]) -> bool {
         constexpr int h0 = decltype(H0)::value;
@@ -757,7 +689,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
             ok = (LV_P16_ABL & 2) ? true : rs4_all_tagged(u, want);
             ok = __all(ok);
             if (!ok && ++spins > SPIN_LIMIT) { s_abort = 1; return false; }
-            if (!ok) lv_poll_backoff();
         } while (!ok);
         LV_TRACE_ONLY(tr_spins[0] = spins;)
         float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
@@ -783,7 +714,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
                 ok = (LV_P16_ABL & 2) ? true : rs4_all_tagged(u, want);
                 ok = __all(ok);
                 if (!ok && ++spins > SPIN_LIMIT) { s_abort = 1; return false; }
-                if (!ok) lv_poll_backoff();
             } while (!ok);
             LV_TRACE_ONLY(tr_spins[q ? 1 : 0] = spins;)
             float a[2], b[2], c[2], d[2];
@@ -813,12 +743,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_persist_rs16_kernel(Bwd16P p) {
         if (!receive_round(lv_const<0>(), src, want, dh_rec)) return false;
         if constexpr (NB > HB) {
             if (!receive_round(lv_const<HB>(), src, want, dh_rec)) return false;
-        }
-        if constexpr (NB > 2 * HB) {                  // (LV_HB16 = 1 at 16 rows: four rounds; the shipped HB = 2 stops above)
-            if (!receive_round(lv_const<2 * HB>(), src, want, dh_rec)) return false;
-        }
-        if constexpr (NB > 3 * HB) {
-            if (!receive_round(lv_const<3 * HB>(), src, want, dh_rec)) return false;
         }
         return true;
     };
