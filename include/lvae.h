@@ -582,6 +582,40 @@ int lv_mh_step_f32(const float* cond_ll, float* prop, float* cur, float* cur_ll,
                    const float* eps_next, float std, float* samples, int rows, int C, int nz, int nsamples, int keep, int init,
                    float* ratio_out, int* accept_out, void* stream);
 
+/* ---- annealed importance sampling of log p(x) (lv_ais.hip): VAE.nll_ais (Neal 2001; Wu et al. 2017).  The transitions are
+ * the random-walk Metropolis kernel above on the annealed target q0(z)^(1 - beta) p(z, x)^beta; every chain carries a log-weight.
+ *   q0      = N(mu0, diag exp(lv0)), mu0 / lv0 [B][nz]; both NULL: the prior N(0, I)
+ *   g(z)    = (log p(z) - log q0(z)) + log p(x|z)           float32; with the prior as q0 the pair is skipped, g = log p(x|z)
+ *   z_0     ~ q0,  logw = 0 (float64)
+ *   for i = 1..N:
+ *       logw += (beta_i - beta_{i-1}) * (double) g(cur)      float64 accumulate, beta a float64 array
+ *       next  = eps_i * std_i + cur                          rounded product, then rounded sum
+ *       ratio = [log q0(next) + (float)beta_i * g(next)] - [log q0(cur) + (float)beta_i * g(cur)]
+ *       accept = ratio >= 0 || u_i < expf(ratio)             select, never blend; a NaN ratio rejects
+ *   log p^(x) = logsumexp_c logw_c - log C
+ * State in caller-owned buffers: cur [B][C][nz], g_cur / lq_cur [B][C] (g(cur), log q0(cur)), logw [B][C] float64, accepts
+ * [B][C] int32.  ratio_out / accept_out / logw_out (float / int32 / float64, one per chain and iteration; logw_out: the running
+ * log-weight after the iteration's increment) may be NULL.  eps and u are buffers of standard normal / uniform [0, 1) draws.
+ * lv_ais_chain_f32: the fused route, envelope lv_ais_chain_f32_supported (that of lv_mh_chain_f32); ws is lv_mh_chain_prep_f32's
+ * workspace, unchanged.  n_iter iterations in one launch: eps [n_iter][B][C][nz], u [n_iter][B][C], std_it [n_iter], beta
+ * [n_iter + 1] = the temperature before this launch's first iteration, then one per iteration.  first != 0: score the starting
+ * point in cur first (incoming g_cur / lq_cur / logw / accepts ignored; logw and the counts start at 0). */
+int lv_ais_chain_f32_supported(int V, int ni, int H, int nz, int T);
+int lv_ais_chain_f32(const int64_t* x, int B, int T, const float* ws, int V, int H, int nz, int C, float* cur, float* g_cur,
+                     float* lq_cur, double* logw, int* accepts, const float* eps, const float* u, const double* beta,
+                     const float* std_it, const float* mu0, const float* lv0, int n_iter, int first, float* ratio_out,
+                     int* accept_out, double* logw_out, void* stream);
+/* lv_ais_step_f32: the glue for any decoder, rows = B * C chains, any nz >= 1, one launch per iteration.  cond_ll [rows] =
+ * log p(x|prop) as eval_cond_ll returned it; the launch decides iteration i at temperature beta (= beta_i), selects, counts and
+ * writes ratio_out / accept_out [rows]; then, where eps_next is given, it applies iteration i + 1's increment
+ * logw += dbeta_next * (double) g(cur) (dbeta_next = beta_{i+1} - beta_i, formed in float64 by the caller), writes it to
+ * logw_out_next [rows] and replaces prop by eps_next * std_next + cur.  init != 0: cond_ll was computed at cur = z_0 -- g_cur,
+ * lq_cur, logw = 0, accepts = 0, then iteration 1's increment and proposals as above (u, beta unread). */
+int lv_ais_step_f32(const float* cond_ll, float* prop, float* cur, float* g_cur, float* lq_cur, double* logw, int* accepts,
+                    const float* u, double beta, const float* eps_next, float std_next, double dbeta_next, const float* mu0,
+                    const float* lv0, int rows, int C, int nz, int init, float* ratio_out, int* accept_out,
+                    double* logw_out_next, void* stream);
+
 /* ---- generation helpers (lv_eval.hip; SURVEY.md 8f row 4: modules/decoders/dec_lstm.py:163-367) -------------------------
  * torch.argmax(logits, dim=1) (greedy_decode, dec_lstm.py:304): lowest index among equal maxima */
 int lv_argmax_rows_f32(const float* in, long ld, int R, int C, int64_t* idx, void* stream);

@@ -205,6 +205,10 @@ SIGNATURES = {
     "lv_mh_chain_prep_f32": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "lv_mh_chain_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
     "lv_mh_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "lv_ais_chain_f32_supported": [_i, _i, _i, _i, _i],
+    "lv_ais_chain_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                         _vp, _vp],
+    "lv_ais_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _f, _d, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "lv_beam_supported": [_i, _i, _i],
     "lv_beam_ws_floats": [_i, _i, _i],
     "lv_beam_init_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -251,7 +255,7 @@ class Lib(object):
                            "lv_lstm_persist16_wpk_floats", "lv_lstm_persist16_xch_floats", "lv_lstm_persist16_saved_floats",
                            "lv_pixelcnn_net_words", "lv_pixelcnn_block_words", "lv_conv32_tap_split", "lv_dec_cond_ll_f32_supported",
                            "lv_dec_cond_ll_f32_ws_floats", "lv_beam_supported", "lv_beam_ws_floats", "lv_bn_partial_floats",
-                           "lv_mh_chain_f32_supported", "lv_mh_chain_f32_ws_floats"}
+                           "lv_mh_chain_f32_supported", "lv_mh_chain_f32_ws_floats", "lv_ais_chain_f32_supported"}
 
     def __getattr__(self, name):
         if name.startswith("lv_"):

@@ -1814,6 +1814,70 @@ class LSTMDecoderEngine(object):
         return {"samples": samples, "cur": cur, "log_joint": cur_ll, "accepts": accepts, "ratios": ratios, "flags": flags,
                 "iterations": total}
 
+    def ais_chain(self, x, z0, draw, beta, std_it, mu0=None, lv0=None, iters_per_launch=None):
+        """Annealed importance sampling chains (VAE.nll_ais; the contract is at the top of csrc/lv_ais.hip) through
+        lv_ais_chain_f32: x int64 [B][T], starting points z0 [B][C][nz] drawn from q0 = N(mu0, diag exp(lv0)) (mu0 / lv0 [B][nz];
+        both None: the prior), beta float64 [N + 1] (non-decreasing from 0 to 1; checked by the caller), std_it float32 [N].
+        draw(i0, n) -> (eps [n][B][C][nz], u [n][B][C]) as for mh_chain.  Prep runs once; the chain then runs in launches of at
+        most iters_per_launch iterations (default: mh_default_iters_per_launch(T)) whose cut does not change the result.  The
+        caller checks ais_chain_supported().  Every operand must live on x's device: a mismatch is refused before anything is
+        launched.  Nothing is read back to the host.
+        -> dict(logw [B][C] float64, cur [B][C][nz], g [B][C], accepts [B][C] int32, ratios / flags / logw_trace [N][B][C])."""
+        device = x.device
+        _same_device("ais_chain", device, z0=z0, beta=beta, std_it=std_it, mu0=mu0, lv0=lv0)
+        self.ensure(device)
+        V, ni, H, nz = self.dims()
+        if x.dim() != 2 or x.dtype != torch.int64 or z0.dim() != 3 or z0.shape[0] != x.shape[0] or z0.shape[2] != nz:
+            raise ValueError("ais_chain: x int64 [B][T] and z0 [B][C][%d] expected, got %s %s and %s"
+                             % (nz, x.dtype, tuple(x.shape), tuple(z0.shape)))
+        B, T = x.shape
+        C = z0.shape[1]
+        total = int(std_it.numel())
+        if total < 1 or beta.dim() != 1 or beta.numel() != total + 1 or beta.dtype != torch.float64 or std_it.dim() != 1:
+            raise ValueError("ais_chain: beta float64 [N + 1] and std_it [N], N >= 1, expected")
+        if (mu0 is None) != (lv0 is None) or (mu0 is not None and (tuple(mu0.shape) != (B, nz) or tuple(lv0.shape) != (B, nz))):
+            raise ValueError("ais_chain: mu0 and lv0 [%d][%d] (or both None) expected" % (B, nz))
+        per = self.mh_default_iters_per_launch(T) if iters_per_launch is None else int(iters_per_launch)
+        if per < 1:
+            raise ValueError("ais_chain: iters_per_launch >= 1 expected")
+        chunks = []                                  # every chunk's noise is fetched (and checked) before the first launch
+        for i0 in range(0, total, per):
+            n = min(per, total - i0)
+            eps, u = draw(i0, n)
+            _same_device("ais_chain", device, eps=eps, u=u)
+            if tuple(eps.shape) != (n, B, C, nz) or tuple(u.shape) != (n, B, C):
+                raise ValueError("ais_chain: eps [%d][%d][%d][%d] and u [%d][%d][%d] expected, got %s and %s"
+                                 % (n, B, C, nz, n, B, C, tuple(eps.shape), tuple(u.shape)))
+            chunks.append((i0, n, eps.contiguous().float(), u.contiguous().float()))
+        x = x.contiguous()
+        beta, std_it = beta.contiguous(), std_it.contiguous().float()
+        if mu0 is not None:
+            mu0, lv0 = mu0.detach().contiguous().float(), lv0.detach().contiguous().float()
+        v = self.flat.views
+        s = stream_ptr(device)
+        f32 = dict(dtype=torch.float32, device=device)
+        ws = torch.empty(self.lib.lv_mh_chain_f32_ws_floats(V, H, nz, B, T), **f32)
+        cur = z0.detach().float().contiguous().clone()
+        g, lq = torch.zeros(B, C, **f32), torch.zeros(B, C, **f32)
+        logw = torch.zeros(B, C, dtype=torch.float64, device=device)
+        accepts = torch.zeros(B, C, dtype=torch.int32, device=device)
+        ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, dtype=torch.int32, device=device)
+        trace = torch.empty(total, B, C, dtype=torch.float64, device=device)
+        self.lib.lv_mh_chain_prep_f32(P(x), B, T, P(v["embed.weight"]), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]),
+                                      P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]),
+                                      P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), s)
+        for i0, n, eps, u in chunks:
+            self.lib.lv_ais_chain_f32(P(x), B, T, P(ws), V, H, nz, C, P(cur), P(g), P(lq), P(logw), P(accepts), P(eps), P(u),
+                                      P(beta, i0), P(std_it, i0), P(mu0), P(lv0), n, 1 if i0 == 0 else 0, P(ratios, i0 * B * C),
+                                      P(flags, i0 * B * C), P(trace, i0 * B * C), s)
+        return {"logw": logw, "cur": cur, "g": g, "accepts": accepts, "ratios": ratios, "flags": flags, "logw_trace": trace,
+                "iterations": total}
+
+    def ais_chain_supported(self, T):
+        """True where lv_ais_chain_f32 takes this decoder's shape with T-token sentences."""
+        V, ni, H, nz = self.dims()
+        return bool(self.lib.lv_ais_chain_f32_supported(V, ni, H, nz, int(T)))
+
     def backward(self, drec, gen=None, partial_dz=False):
         """drec [B*ns] = dL/d rec of every decoder row -> fills self.flat.grad; returns dz [B*ns][nz] (partial_dz: the tail kernel's
         partial sums [parts][B*ns][nz] and their count instead).  ns > 1: the gate gradients are summed over a
@@ -2198,6 +2262,42 @@ def mh_step(cond_ll, prop, cur, cur_ll, accepts, u, eps_next, std, samples, keep
         raise ValueError("mh_step: operand shapes do not match cur %s" % (tuple(cur.shape),))
     lib.lv_mh_step_f32(P(cond), P(prop), P(cur), P(cur_ll), P(accepts), P(u), P(eps_next), float(std), P(samples), rows, C, nz,
                        nsamples, int(keep), 1 if init else 0, P(ratio_out), P(flag_out), s)
+
+
+def ais_step(cond_ll, prop, cur, g_cur, lq_cur, logw, accepts, u, beta, eps_next, std_next, dbeta_next, mu0=None, lv0=None,
+             init=False, ratio_out=None, flag_out=None, logw_out_next=None):
+    """One launch of lv_ais_step_f32, the per-iteration glue of VAE.nll_ais for any decoder (contract: csrc/lv_ais.hip):
+    cond_ll [B][C] = log p(x|prop) as eval_cond_ll returned it; prop, cur [B][C][nz], g_cur / lq_cur [B][C] f32, logw [B][C] f64
+    and accepts [B][C] int32 are updated in place.  The launch decides this iteration at temperature `beta`, then (eps_next
+    given) adds the next iteration's increment dbeta_next * g(cur) to logw, records it in logw_out_next and replaces prop by
+    eps_next * std_next + cur.  init: cond_ll was computed at cur = z_0.  beta / dbeta_next are Python floats (float64).  Every
+    operand on one device, contiguous, or it is refused before the launch."""
+    device = cond_ll.device
+    ops = {"prop": prop, "cur": cur, "g_cur": g_cur, "lq_cur": lq_cur, "logw": logw, "accepts": accepts, "u": u,
+           "eps_next": eps_next, "mu0": mu0, "lv0": lv0, "ratio_out": ratio_out, "flag_out": flag_out,
+           "logw_out_next": logw_out_next}
+    for name, t in ops.items():
+        if t is None:
+            continue
+        if t.device != device:
+            raise _lib.LvaeError("ais_step: %s is on %s, cond_ll on %s" % (name, t.device, device))
+        want = (torch.int32 if name in ("accepts", "flag_out") else torch.float64 if name in ("logw", "logw_out_next")
+                else torch.float32)
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError("ais_step: %s must be a contiguous %s tensor" % (name, want))
+    lib, s = backend_for(device), stream_ptr(device)
+    B, C, nz = cur.shape
+    rows = B * C
+    cond = cond_ll.detach().contiguous().float()
+    if (cond.numel() != rows or tuple(prop.shape) != (B, C, nz) or any(t.numel() != rows for t in (g_cur, lq_cur, logw, accepts))
+            or (u is None and not init) or (u is not None and u.numel() != rows)
+            or (eps_next is not None and eps_next.numel() != rows * nz) or (mu0 is None) != (lv0 is None)
+            or (mu0 is not None and (tuple(mu0.shape) != (B, nz) or tuple(lv0.shape) != (B, nz)))
+            or any(t is not None and t.numel() != rows for t in (ratio_out, flag_out, logw_out_next))):
+        raise ValueError("ais_step: operand shapes do not match cur %s" % (tuple(cur.shape),))
+    lib.lv_ais_step_f32(P(cond), P(prop), P(cur), P(g_cur), P(lq_cur), P(logw), P(accepts), P(u), float(beta), P(eps_next),
+                        float(std_next), float(dbeta_next), P(mu0), P(lv0), rows, C, nz, 1 if init else 0, P(ratio_out),
+                        P(flag_out), P(logw_out_next), s)
 
 
 def calc_mi(mu, logvar, z):

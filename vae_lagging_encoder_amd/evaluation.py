@@ -60,6 +60,28 @@ def calc_iwnll(model, test_data_batch, args, ns=100, verbose=False, np_rng=None)
     return nll, ppl
 
 
+def calc_aisnll(model, test_data_batch, args, np_rng=None, verbose=False, **ais_kwargs):
+    """calc_iwnll's bookkeeping over VAE.nll_ais (annealed importance sampling: an estimate of log p(x) that does not lean on
+    the encoder).  ais_kwargs go to nll_ais (chains, temps, transitions, std, schedule, init, generator, ...); std defaults to
+    args.ais_std as nll_ais reads it from model.args.  Returns (nll, ppl)."""
+    if "std" not in ais_kwargs and hasattr(args, "ais_std"):
+        ais_kwargs = dict(ais_kwargs, std=args.ais_std)
+    tot = []
+    report_num_words = report_num_sents = 0
+    for i in (np_rng if np_rng is not None else np.random).permutation(len(test_data_batch)):
+        batch_data = test_data_batch[i]
+        batch_size, sent_len = batch_data.size()
+        report_num_words += (sent_len - 1) * batch_size
+        report_num_sents += batch_size
+        tot.append(model.nll_ais(batch_data, **ais_kwargs).sum())
+    report_nll_loss = float(torch.stack(tot).sum().item())
+    nll = report_nll_loss / report_num_sents
+    ppl = math.exp(nll * report_num_sents / report_num_words)
+    if verbose:
+        print("ais nll: %.4f, ais ppl: %.4f" % (nll, ppl))
+    return nll, ppl
+
+
 def calc_mi(model, test_data_batch):
     """text.py:186-198: batch-size-weighted mean of the per-batch mutual information estimates."""
     mi = 0.0
@@ -123,6 +145,32 @@ def image_calc_amortization_gap(model, test_loader, steps=20, nsamples=1, **refi
     return _amortization_gap(model, (batch_data for batch_data, _ in test_loader), steps, nsamples, refine_kwargs)
 
 
+def calc_inference_gaps(model, test_data_batch, steps=20, nsamples=1, np_rng=None, ais=None, **refine_kwargs):
+    """The inference-gap decomposition of Cremer et al. 2018 in nats per sentence, one pass over the batches (random order, as
+    calc_iwnll visits them), kl_weight = 1:  log p(x) - ELBO(encoder) = approximation gap + amortization gap, with log p(x) the
+    AIS estimate (VAE.nll_ais, `ais` = its keyword arguments), ELBO(encoder) and ELBO(refined) from one refine_posterior trace on
+    shared noise (calc_amortization_gap's two numbers).  approximation_gap = log_px - elbo_svi, amortization_gap = elbo_svi -
+    elbo_enc: the two sum to log_px - elbo_enc by construction.  Returns dict(log_px, elbo_enc, elbo_svi, amortization_gap,
+    approximation_gap, n)."""
+    if "kl_weight" in refine_kwargs and float(refine_kwargs["kl_weight"]) != 1.0:
+        raise ValueError("calc_inference_gaps: the decomposition holds for kl_weight = 1 only")
+    ais = dict(ais or {})
+    enc, svi, lpx = [], [], []
+    n = 0
+    for i in (np_rng if np_rng is not None else np.random).permutation(len(test_data_batch)):
+        batch_data = test_data_batch[i]
+        info = model.refine_posterior(batch_data, steps=steps, nsamples=nsamples, return_info=True, **refine_kwargs)[2]
+        enc.append(info["loss0"].sum())
+        svi.append(info["loss"].sum())
+        lpx.append(-model.nll_ais(batch_data, **ais).sum())
+        n += batch_data.size(0)
+    elbo_enc = -float(torch.stack(enc).sum().item()) / n
+    elbo_svi = -float(torch.stack(svi).sum().item()) / n
+    log_px = float(torch.stack(lpx).sum().item()) / n
+    return {"log_px": log_px, "elbo_enc": elbo_enc, "elbo_svi": elbo_svi, "amortization_gap": elbo_svi - elbo_enc,
+            "approximation_gap": log_px - elbo_svi, "n": n}
+
+
 # ---- image side (reference image.py:96-187): the loaders yield (batch, label) pairs like DataLoader(TensorDataset(x, y)) --------
 def image_test(model, test_loader, mode, args=None, verbose=True):
     """image.py:96-128: loss / KL / reconstruction over one pass of the loader (eval mode is the caller's), then calc_mi over a
@@ -183,4 +231,19 @@ def image_calc_iwnll(model, test_loader, args, verbose=False):
     nll = float(torch.stack(tot).sum().item()) / report_num_examples
     if verbose:
         print("iw nll: %.4f" % nll)
+    return nll
+
+
+def image_calc_aisnll(model, test_loader, args, verbose=False, **ais_kwargs):
+    """calc_aisnll over one pass of a loader of (batch, label) pairs, per example (the step route: PixelCNN decoder)."""
+    if "std" not in ais_kwargs and hasattr(args, "ais_std"):
+        ais_kwargs = dict(ais_kwargs, std=args.ais_std)
+    tot = []
+    report_num_examples = 0
+    for batch_data, _ in test_loader:
+        report_num_examples += batch_data.size(0)
+        tot.append(model.nll_ais(batch_data, **ais_kwargs).sum())
+    nll = float(torch.stack(tot).sum().item()) / report_num_examples
+    if verbose:
+        print("ais nll: %.4f" % nll)
     return nll

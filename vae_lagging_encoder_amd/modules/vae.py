@@ -387,6 +387,185 @@ class VAE(nn.Module):
                          flag_out=flags[it])
         return samples, cur_ll, accepts, ratios, flags
 
+    # True: nll_ais takes the fused chain kernel (lv_ais_chain_f32) where _fused_ais_ok allows it; False forces the
+    # per-iteration route (A/B runs, tests)
+    fused_ais = True
+
+    def _fused_ais_ok(self, x, z0):
+        """Route "chain" of nll_ais: the conditions of _fused_mh_ok with the AIS kernel's own envelope."""
+        dec = self.decoder
+        eng = getattr(dec, "_hip", None)
+        if not (self.fused_ais and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.int64 and z0.device == x.device):
+            return False
+        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
+            return False
+        try:
+            eng.ensure(x.device)
+        except _lib.LvaeError:
+            return False
+        return eng.ais_chain_supported(x.size(1))
+
+    @staticmethod
+    def ais_schedule(schedule, temps, transitions=1):
+        """The per-iteration temperatures of nll_ais as a list of temps * transitions + 1 Python floats (float64): "sigmoid"
+        (Wu et al. 2017: the logistic function on linspace(-4, 4), rescaled to [0, 1]), "linear", or an explicit sequence of
+        temps + 1 values starting at 0, ending at 1 and non-decreasing; every temperature after the first is repeated
+        `transitions` times (further transitions at the same temperature: their log-weight increment is 0)."""
+        temps, transitions = int(temps), int(transitions)
+        if temps < 1 or transitions < 1:
+            raise ValueError("nll_ais: temps >= 1 and transitions >= 1 expected")
+        if isinstance(schedule, str):
+            if schedule == "sigmoid":
+                s = torch.sigmoid(torch.linspace(-4.0, 4.0, temps + 1, dtype=torch.float64))
+                b = ((s - s[0]) / (s[-1] - s[0])).tolist()
+            elif schedule == "linear":
+                b = torch.linspace(0.0, 1.0, temps + 1, dtype=torch.float64).tolist()
+            else:
+                raise ValueError("nll_ais: schedule 'sigmoid', 'linear' or a sequence of temps + 1 values expected, got %r"
+                                 % (schedule,))
+            b[0], b[-1] = 0.0, 1.0
+        else:
+            b = [float(v) for v in (schedule.tolist() if torch.is_tensor(schedule) else schedule)]
+            if len(b) != temps + 1:
+                raise ValueError("nll_ais: a schedule of temps + 1 = %d values expected, got %d" % (temps + 1, len(b)))
+            if b[0] != 0.0 or b[-1] != 1.0 or any(not (b[i + 1] >= b[i]) for i in range(temps)):
+                raise ValueError("nll_ais: the schedule must start at 0, end at 1 and be non-decreasing")
+        return [b[0]] + [v for v in b[1:] for _ in range(transitions)]
+
+    def nll_ais(self, x, chains=16, temps=500, transitions=1, std=None, schedule="sigmoid", init="prior", noise=None,
+                generator=None, iters_per_launch=None, return_info=False):
+        """Annealed importance sampling estimate of -log p(x) (Neal 2001; Wu et al. 2017) -> (batch,) float32 on x's device,
+        computed under torch.no_grad().  Unlike nll_iw the estimate does not lean on the encoder: `chains` chains per sentence
+        start at a draw from q0 -- the prior (init="prior") or q(z|x) (init="encoder") -- and move through N = temps *
+        transitions random-walk Metropolis transitions (the kernel of sample_from_posterior) on the targets
+        q0^(1 - beta_i) p(z, x)^beta_i, beta from 0 to 1 (ais_schedule); a chain's log-weight is the float64 sum of
+        (beta_i - beta_{i-1}) g(z_{i-1}), g = log p(z, x) - log q0(z), and log p^(x) = logsumexp_c logw_c - log chains (the
+        [batch][chains] epilogue is torch, in float64).  The contract, formula by formula, is at the top of csrc/lv_ais.hip.
+
+        std: the proposal scale, a float or a sequence of N floats; default args.ais_std.  There is no built-in value: none
+        would be right for both the prior's width and a trained posterior's.  Tune it by info["accept_rate_iter"].
+        noise = (z0 [B][chains][nz], eps [N][B][chains][nz], u [N][B][chains]) injects every random draw; without it z0, eps
+        and u are drawn on x's device (`generator` optional), eps / u one pair per launch chunk as sample_from_posterior does.
+
+        Routes (class switch fused_ais = False forces the second):
+          "chain": eval-mode LSTM decoder inside lv_ais_chain_f32's envelope -- the whole chain on the device in launches of at
+                   most iters_per_launch iterations, 16 chains of a sentence per workgroup;
+          "step":  everything else (H > 128, the PixelCNN decoder, a training-mode decoder with dropout, variable-length
+                   pairs): one eval_cond_ll(x, next) plus one lv_ais_step_f32 launch per iteration.
+        Neither reads anything back to the host inside the chain.
+
+        return_info: also {"logw": [B, chains] float64, "accept_rate": [B, chains], "accept_rate_iter": [N], "route",
+        "iterations", "se": [B] (the delta-method standard error of log p^: sqrt(var_c(w_c / mean w) / chains); nan for one
+        chain), "ratios" / "accepts" / "logw_trace": [N, B, chains]}."""
+        chains = int(chains)
+        if chains < 1:
+            raise ValueError("nll_ais: chains >= 1 expected")
+        beta = self.ais_schedule(schedule, temps, transitions)
+        total = len(beta) - 1
+        if init not in ("prior", "encoder"):
+            raise ValueError("nll_ais: init 'prior' or 'encoder' expected, got %r" % (init,))
+        if std is None:
+            if not hasattr(self.args, "ais_std"):
+                raise ValueError("nll_ais: pass std or set args.ais_std (there is no default proposal scale)")
+            std = self.args.ais_std
+        if torch.is_tensor(std):
+            std = std.tolist()
+        stds = [float(v) for v in std] if isinstance(std, (list, tuple)) else [float(std)] * total
+        if len(stds) != total or any(not (v >= 0.0) for v in stds):
+            raise ValueError("nll_ais: std must be a float >= 0 or a sequence of temps * transitions = %d of them" % total)
+        x = self._batch(x)
+        with torch.no_grad():
+            dev = x.device if torch.is_tensor(x) else x[0].device
+            B = x.size(0) if torch.is_tensor(x) else x[0].size(0)
+            nz = self.nz
+            if noise is not None:
+                z0, eps_all, u_all = noise
+                for name, t in (("z0", z0), ("eps", eps_all), ("u", u_all)):
+                    if t.device != dev:          # the kernels take raw pointers: refused before anything is launched
+                        raise _lib.LvaeError("nll_ais: %s is on %s, x on %s" % (name, t.device, dev))
+                if (tuple(z0.shape) != (B, chains, nz) or tuple(eps_all.shape) != (total, B, chains, nz)
+                        or tuple(u_all.shape) != (total, B, chains)):
+                    raise ValueError("nll_ais: noise z0 [%d][%d][%d], eps [%d][%d][%d][%d], u [%d][%d][%d] expected, got %s, %s, %s"
+                                     % (B, chains, nz, total, B, chains, nz, total, B, chains, tuple(z0.shape),
+                                        tuple(eps_all.shape), tuple(u_all.shape)))
+            mu0 = lv0 = None
+            if init == "encoder":
+                if noise is None:
+                    z0, (mu0, lv0) = self.encoder.sample(x, chains)
+                else:
+                    mu0, lv0 = self.encode_stats(x)
+                mu0, lv0 = mu0.detach().float().contiguous(), lv0.detach().float().contiguous()
+            elif noise is None:
+                z0 = torch.randn(B, chains, nz, device=dev, generator=generator)
+            if noise is None:
+                eps_all = u_all = None
+            z0 = z0.detach().float().contiguous()
+
+            def draw(i0, n):
+                if eps_all is not None:
+                    return eps_all[i0:i0 + n].float().contiguous(), u_all[i0:i0 + n].float().contiguous()
+                return (torch.randn(n, B, chains, nz, device=dev, generator=generator),
+                        torch.rand(n, B, chains, device=dev, generator=generator))
+
+            if self._fused_ais_ok(x, z0):
+                route = "chain"
+                r = self.decoder._hip.ais_chain(x, z0, draw, torch.tensor(beta, dtype=torch.float64, device=dev),
+                                                torch.tensor(stds, dtype=torch.float32, device=dev), mu0, lv0, iters_per_launch)
+            else:
+                route = "step"
+                r = self._ais_by_steps(x, z0, draw, beta, stds, mu0, lv0, iters_per_launch)
+            logw = r["logw"]
+            log_px = torch.logsumexp(logw, dim=1) - math.log(chains)
+            nll = (-log_px).float()
+            if not return_info:
+                return nll
+            w = torch.exp(logw - logw.max(dim=1, keepdim=True)[0])
+            w = w / w.mean(dim=1, keepdim=True)
+            se = torch.sqrt(w.var(dim=1, unbiased=True) / chains) if chains > 1 else torch.full_like(log_px, float("nan"))
+            flags = r["flags"]
+        return nll, {"logw": logw, "accept_rate": r["accepts"].float() / float(total),
+                     "accept_rate_iter": flags.float().mean(dim=(1, 2)), "route": route, "iterations": total, "se": se,
+                     "ratios": r["ratios"], "accepts": flags, "logw_trace": r["logw_trace"], "beta": beta, "std": stds}
+
+    def _ais_by_steps(self, x, z0, draw, beta, stds, mu0, lv0, iters_per_launch):
+        """Route "step" of nll_ais: eval_cond_ll for the scores, lv_ais_step_f32 for everything else.  The launch that decides
+        iteration i also applies iteration i + 1's increment and writes its proposals: one launch per iteration."""
+        dev = z0.device
+        B, C, nz = z0.shape
+        total = len(stds)
+        if iters_per_launch is None:
+            T = x.size(1) if (torch.is_tensor(x) and x.dim() == 2) else 33
+            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
+        per = int(iters_per_launch)
+        if per < 1:
+            raise ValueError("nll_ais: iters_per_launch >= 1 expected")
+        f32, i32, f64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.float64))
+        cur, prop = z0.clone(), z0.clone()
+        g, lq, logw, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **f32), torch.zeros(B, C, **f64), torch.zeros(B, C, **i32)
+        ratios, flags, trace = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32), torch.empty(total, B, C, **f64)
+        eps, u = draw(0, min(per, total))
+        c0 = 0                                                    # first iteration of the chunk (eps, u) covers
+        try:
+            cond0 = self.eval_cond_ll(x, cur)
+        except (TypeError, AttributeError) as e:
+            if torch.is_tensor(x):
+                raise
+            raise ValueError("nll_ais: this decoder's eval_cond_ll does not take a variable-length pair (%s)" % e)
+        _eng.ais_step(cond0, prop, cur, g, lq, logw, accepts, None, 0.0, eps[0], stds[0], beta[1] - beta[0],
+                      mu0, lv0, init=True, logw_out_next=trace[0])
+        for it in range(total):                                   # iteration it + 1 of the contract, at beta[it + 1]
+            cond = self.eval_cond_ll(x, prop)
+            u_it = u[it - c0]
+            more = it + 1 < total
+            if more and it + 1 - c0 >= eps.shape[0]:
+                c0 = it + 1
+                eps, u = draw(c0, min(per, total - c0))
+            _eng.ais_step(cond, prop, cur, g, lq, logw, accepts, u_it, beta[it + 1], eps[it + 1 - c0] if more else None,
+                          stds[it + 1] if more else 0.0, beta[it + 2] - beta[it + 1] if more else 0.0, mu0, lv0,
+                          ratio_out=ratios[it], flag_out=flags[it], logw_out_next=trace[it + 1] if more else None)
+        return {"logw": logw, "cur": cur, "g": g, "accepts": accepts, "ratios": ratios, "flags": flags, "logw_trace": trace}
+
     # True: refine_posterior takes the engine's refinement session (lv_svi_step_f32, lv_dec_tail_dz_f32) where _fused_svi_ok
     # allows it; False forces the generic route (A/B runs, the tests' second oracle, the bench baseline)
     fused_svi = True
