@@ -616,6 +616,31 @@ int lv_ais_step_f32(const float* cond_ll, float* prop, float* cur, float* g_cur,
                     const float* lv0, int rows, int C, int nz, int init, float* ratio_out, int* accept_out,
                     double* logw_out_next, void* stream);
 
+/* ---- Hamiltonian transitions for the chains above (lv_hmc.hip): VAE.nll_ais(transition="hmc"),
+ * VAE.sample_from_posterior(transition="hmc").  The contract, with the float32 evaluation order of every expression, is at the
+ * top of lv_hmc.hip; q0, g, the accept rule, the float64 beta and logw are those of lv_ais.hip.  With rec(z) = -log p(x|z) and
+ * d(z) = d rec / d z from one decoder forward + backward to z on all rows = B * C chains (row b * C + c):
+ *   grad U_beta(z)_j = a_j + (float)beta * ((z_j - a_j) + d_j),  a_j = (z_j - mu0_j) * expf(-lv0_j)   (prior: z_j + beta * d_j)
+ *   for i = 1..N:  logw += (beta_i - beta_{i-1}) * (double) g(cur);  p <- mom_i;  K0 = 0.5 |p|^2
+ *                  p <- p - (eps / 2) grad U(cur)     (from the cached d(cur));   L times: z <- z + eps p, score z, kick (the
+ *                  last kick a half one);  dH = [log q0(z) + beta_i g(z)] - [log q0(cur) + beta_i g(cur)] + K0 - 0.5 |p|^2
+ *                  accept = dH >= 0 || u_i < expf(dH);  select;  eps <- min(max(eps * (accepted ? up : down), eps_min), eps_max)
+ * lv_hmc_leap_f32 is one launch after every decoder pass.  rec [rows], dz [parts][rows][nz] (lv_dec_tail_dz_f32's partial
+ * sums; parts = 1: a plain gradient).  In flight: pos [rows][nz] (the decoder's z input), mom [rows][nz], k0 [rows].  State: cur
+ * [rows][nz], g_cur / lq_cur / rec_cur [rows], d_cur [rows][nz], logw [rows] float64, accepts [rows] int32, eps [rows].
+ *   mode 0 (init): the pass scored z_0 = pos -- store the state, logw = 0, accepts = 0, then open transition 1;
+ *   mode 1 (mid):  full kick at beta, drift, write mom / pos (needs L >= 2);
+ *   mode 2 (last): half kick at beta, dH, the decision with u [rows], select, count, adapt, then open the next transition.
+ * Opening (mom_next [rows][nz] given): logw += dbeta_next * (double) g(cur) -> logw_out_next, p <- mom_next, K0 -> k0, half kick
+ * at beta_next from d_cur, drift -> pos.  mom_next NULL: no transition follows, only the state is written.  beta, beta_next and
+ * dbeta_next = beta_next - beta are formed in float64 by the caller.  dh_out / flag_out [rows] (mode 2), logw_out_next [rows],
+ * keep_out [rows][nz] (the selected cur; modes 0 and 2) may be NULL.  Nothing is written when an argument is refused. */
+int lv_hmc_leap_f32(const float* rec, const float* dz, int parts, float* pos, float* mom, float* k0, float* cur, float* g_cur,
+                    float* lq_cur, float* rec_cur, float* d_cur, double* logw, int* accepts, float* eps, const float* u,
+                    const float* mom_next, double beta, double beta_next, double dbeta_next, const float* mu0, const float* lv0,
+                    int rows, int C, int nz, int L, int mode, float up, float down, float eps_min, float eps_max, float* dh_out,
+                    int* flag_out, double* logw_out_next, float* keep_out, void* stream);
+
 /* ---- generation helpers (lv_eval.hip; SURVEY.md 8f row 4: modules/decoders/dec_lstm.py:163-367) -------------------------
  * torch.argmax(logits, dim=1) (greedy_decode, dec_lstm.py:304): lowest index among equal maxima */
 int lv_argmax_rows_f32(const float* in, long ld, int R, int C, int64_t* idx, void* stream);

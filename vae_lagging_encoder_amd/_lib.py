@@ -209,6 +209,8 @@ SIGNATURES = {
     "lv_ais_chain_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
                          _vp, _vp],
     "lv_ais_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _f, _d, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "lv_hmc_leap_f32": [_vp, _vp, _i] + [_vp] * 13 + [_d, _d, _d, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp,
+                        _vp],
     "lv_beam_supported": [_i, _i, _i],
     "lv_beam_ws_floats": [_i, _i, _i],
     "lv_beam_init_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

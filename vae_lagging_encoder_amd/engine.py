@@ -2051,6 +2051,57 @@ class LSTMDecoderEngine(object):
             return sv
         return c.get(("svi", B, ns, Td), build)
 
+    # A frozen-decoder pass at the z in sv.z, shared by svi_refine and hmc_ais: _zpass_begin once per call, then per pass
+    # _zpass_forward (leaves w.rec) and _zpass_dz (the gradient of sum_row sv.rowscale[row] * rec[row] with respect to z).
+    def _zpass_begin(self, x, ns, w, sv):
+        """Exact f32: the z-independent work -- embedding gather, the word half of the input projection (sv.Gxw), the targets in
+        decoder row order.  -> the token ids the per-row kernels read.  bf16: nothing (forward() repeats its own)."""
+        if self.precision != "f32":
+            return x
+        B, T = x.shape
+        Td = T - 1
+        lib, s = self.lib, stream_ptr(x.device)
+        V, ni, H, nz = self.dims()
+        v = self.flat.views
+        ids = x
+        lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, None, 1.0, P(w.X), Td, B, ni, V, s)
+        _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(v["lstm.weight_ih_l0"]), ni + nz, P(sv.Gxw), 4 * H, prec=self.precision)
+        if ns > 1:
+            lib.lv_repeat_rows_i64(P(x), P(w.x_rep), B, T, ns, s)
+            ids = w.x_rep
+        _gx_buffer(self.wsc, w, Td * B * ns, H)
+        self.last_steps = None                         # equal-length BPTT, whatever the last forward() was given
+        return ids
+
+    def _zpass_forward(self, x, ids, ns, w, sv):
+        B, T = x.shape
+        V, ni, H, nz = self.dims()
+        if self.precision != "f32":
+            self.forward(x, sv.z.view(B, ns, nz), None, None, 0.0, 0.0)
+            return
+        Td, Bd = T - 1, B * ns
+        lib, s = self.lib, stream_ptr(x.device)
+        v = self.flat.views
+        lib.lv_dec_init_f32(P(sv.z), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]), ni + nz, ni, P(v["lstm.bias_ih_l0"]),
+                            P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 0, Bd, H, nz, s)
+        lib.lv_gx_expand_add_f32(P(sv.Gxw), P(w.Zp), P(w.Gx), Td, B, ns, 4 * H, s)
+        _lstm_forward(self, lib, s, None, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, P(w.O), Td, Bd, H, x.device)
+        _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
+        lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
+        lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
+
+    def _zpass_dz(self, x, ids, ns, w, sv):
+        """-> (the dz tail's partial sums [parts][B*ns][nz], parts)"""
+        if self.precision != "f32":
+            return self.backward_dz(sv.rowscale, partial_dz=True)
+        B, T = x.shape
+        Td, Bd = T - 1, B * ns
+        lib, s = self.lib, stream_ptr(x.device)
+        V, ni, H, nz = self.dims()
+        self._bwd_dlogits(lib, s, w, None, ids, sv.rowscale, T, Td, Bd, V)
+        self._bwd_dO_bptt(lib, s, w, None, None, None, 1.0, Td, Bd, V, H, x.device)
+        return self._bwd_tail_dz(lib, s, w, Bd, H, ni, nz, True)
+
     def svi_refine(self, x, mulv, eps, steps, lr, momentum, clip, kl_weight):
         """`steps` SVI iterations on every sentence's phi = (mu | logvar) with this decoder frozen and in eval arithmetic (no dropout):
         x int64 [B][T], mulv [B][2nz] (the starting point; not modified), eps [B][ns][nz] (the same in every iteration).  steps + 1
@@ -2068,17 +2119,15 @@ class LSTMDecoderEngine(object):
         Td = T - 1
         dev = x.device
         _same_device("svi_refine", dev, mulv=mulv, eps=eps)
-        f = self.ensure(dev)
-        V, ni, H, nz = self.dims()
+        self.ensure(dev)
+        nz = self.dims()[3]
         if tuple(mulv.shape) != (B, 2 * nz) or eps.dim() != 3 or eps.shape[0] != B or eps.shape[2] != nz or eps.shape[1] < 1:
             raise ValueError("svi_refine: mulv [%d][%d] and eps [%d][ns][%d] expected, got %s and %s"
                              % (B, 2 * nz, B, nz, tuple(mulv.shape), tuple(eps.shape)))
         ns = int(eps.shape[1])
         Bd = B * ns
         lib, s = self.lib, stream_ptr(dev)
-        v = f.views
         eps = eps.detach().float().contiguous()
-        exact = self.precision == "f32"
         sv = self._svi_ws(B, ns, Td)
         f32 = dict(dtype=torch.float32, device=dev)
         phi = mulv.detach().float().contiguous().clone()
@@ -2090,29 +2139,11 @@ class LSTMDecoderEngine(object):
         sv.klw.fill_(float(kl_weight))
         sv.rowscale.fill_(1.0 / ns)
         w = self._ws(Bd, Td, ns)
-        wih = v["lstm.weight_ih_l0"]
-        ids = x
-        if exact:
-            lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, None, 1.0, P(w.X), Td, B, ni, V, s)
-            _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(wih), ni + nz, P(sv.Gxw), 4 * H, prec=self.precision)
-            if ns > 1:
-                lib.lv_repeat_rows_i64(P(x), P(w.x_rep), B, T, ns, s)
-                ids = w.x_rep
-            _gx_buffer(self.wsc, w, Td * Bd, H)
-            self.last_steps = None                     # equal-length BPTT, whatever the last forward() was given
+        ids = self._zpass_begin(x, ns, w, sv)
         kl, kl_next = sv.kl
         lib.lv_reparam_kl_fwd_f32(P(phi), P(eps), P(sv.z), P(kl), B, ns, nz, s)
         for k in range(steps + 1):
-            if exact:
-                lib.lv_dec_init_f32(P(sv.z), P(v["trans_linear.weight"]), P(wih), ni + nz, ni, P(v["lstm.bias_ih_l0"]),
-                                    P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 0, Bd, H, nz, s)
-                lib.lv_gx_expand_add_f32(P(sv.Gxw), P(w.Zp), P(w.Gx), Td, B, ns, 4 * H, s)
-                _lstm_forward(self, lib, s, None, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, P(w.O), Td, Bd, H, dev)
-                _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
-                lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
-                lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
-            else:
-                self.forward(x, sv.z.view(B, ns, nz), None, None, 0.0, 0.0)
+            self._zpass_forward(x, ids, ns, w, sv)
             torch.sum(w.rec.view(B, ns), dim=1, out=rec_trace[k])
             rec_trace[k].div_(ns)
             kl_trace[k].copy_(kl)
@@ -2120,17 +2151,50 @@ class LSTMDecoderEngine(object):
                 lib.lv_svi_step_f32(P(w.rec), None, 0, None, P(kl), P(sv.klw), float(lr), float(momentum), float(clip), P(phi), None,
                                     P(best), P(best_loss), P(trace, k * B), None, None, B, ns, nz, s)
                 break
-            if exact:
-                self._bwd_dlogits(lib, s, w, None, ids, sv.rowscale, T, Td, Bd, V)
-                self._bwd_dO_bptt(lib, s, w, None, None, None, 1.0, Td, Bd, V, H, dev)
-                dzp, parts = self._bwd_tail_dz(lib, s, w, Bd, H, ni, nz, True)
-            else:
-                dzp, parts = self.backward_dz(sv.rowscale, partial_dz=True)
+            dzp, parts = self._zpass_dz(x, ids, ns, w, sv)
             lib.lv_svi_step_f32(P(w.rec), P(dzp), parts, P(eps), P(kl), P(sv.klw), float(lr), float(momentum), float(clip), P(phi),
                                 P(vel), P(best), P(best_loss), P(trace, k * B), P(sv.z), P(kl_next), B, ns, nz, s)
             kl, kl_next = kl_next, kl
         self.gen += 1                                  # the workspaces no longer hold what the last forward() left
         return {"last": phi, "best": best, "best_loss": best_loss, "trace": trace, "rec_trace": rec_trace, "kl_trace": kl_trace}
+
+    # ---- Hamiltonian chains (VAE.nll_ais / sample_from_posterior with transition="hmc") --------------------------
+    def hmc_ais(self, x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep=None, iters_per_launch=None):
+        """C annealed HMC chains per sentence with this decoder frozen and in eval arithmetic (contract: csrc/lv_hmc.hip): x int64
+        [B][T], z0 [B][C][nz], the other arguments and the result as hmc_chain's.  1 + N * L decoder passes for N = len(beta) - 1
+        transitions, each followed by one lv_hmc_leap_f32 launch.  Exact-f32 configuration: the z-independent work runs once
+        (svi_refine's), a pass is lv_dec_init_f32, lv_gx_expand_add_f32, the recurrence, the vocabulary projection + NLL, the
+        softmax backward with drec = 1 per row, dO, the BPTT and lv_dec_tail_dz_f32.  bf16: forward() as it is, then backward_dz().
+        The caller checks svi_supported(B, C).  Nothing is read back inside the chain; a timed-out persistent launch raises after
+        it and returns nothing."""
+        x = x.contiguous()
+        B, T = x.shape
+        dev = x.device
+        _same_device("hmc_ais", dev, z0=z0, mu0=mu0, lv0=lv0)
+        self.ensure(dev)
+        nz = self.dims()[3]
+        if z0.dim() != 3 or z0.shape[0] != B or z0.shape[2] != nz or z0.shape[1] < 1:
+            raise ValueError("hmc_ais: z0 [%d][C][%d] expected, got %s" % (B, nz, tuple(z0.shape)))
+        C = int(z0.shape[1])
+        sv = self._svi_ws(B, C, T - 1)
+        w = self._ws(B * C, T - 1, C)
+        sv.rowscale.fill_(1.0)
+        box = {}
+
+        def score():
+            if not box:                                # first pass: the noise has been checked, nothing was launched before it
+                sv.z.copy_(z0.detach().float().reshape(B * C, nz))
+                box["ids"] = self._zpass_begin(x, C, w, sv)
+            self._zpass_forward(x, box["ids"], C, w, sv)
+            dzp, parts = self._zpass_dz(x, box["ids"], C, w, sv)
+            return w.rec, dzp, parts
+        try:
+            r = hmc_chain(score, sv.z.view(B, C, nz), draw, beta, L, step_size, adapt, mu0, lv0, keep,
+                          self.mh_default_iters_per_launch(T) if iters_per_launch is None else iters_per_launch)
+        finally:
+            self.gen += 1                              # the workspaces no longer hold what the last forward() left
+        check_persistent_status(self)
+        return r
 
 
 def fused_ends_ok(B, nz, ns=1):
@@ -2298,6 +2362,108 @@ def ais_step(cond_ll, prop, cur, g_cur, lq_cur, logw, accepts, u, beta, eps_next
     lib.lv_ais_step_f32(P(cond), P(prop), P(cur), P(g_cur), P(lq_cur), P(logw), P(accepts), P(u), float(beta), P(eps_next),
                         float(std_next), float(dbeta_next), P(mu0), P(lv0), rows, C, nz, 1 if init else 0, P(ratio_out),
                         P(flag_out), P(logw_out_next), s)
+
+
+HMC_INIT, HMC_MID, HMC_LAST = 0, 1, 2
+
+
+def hmc_leap(rec, dz, st, mode, L, u=None, mom_next=None, beta=0.0, beta_next=0.0, dbeta_next=0.0, mu0=None, lv0=None, up=1.0,
+             down=1.0, eps_min=0.0, eps_max=float("inf"), dh_out=None, flag_out=None, logw_out_next=None, keep_out=None):
+    """One launch of lv_hmc_leap_f32, the sampler's side of a decoder pass (contract: csrc/lv_hmc.hip).  rec [B*C] and dz
+    [parts][B*C][nz] (or [B][C][nz]) are the pass at st["pos"]; st holds the chains' buffers, all updated in place: pos, mom, cur,
+    d_cur [B][C][nz], k0, g_cur, lq_cur, rec_cur, eps [B][C] f32, logw [B][C] f64, accepts [B][C] int32.  mode HMC_INIT / HMC_MID /
+    HMC_LAST; beta / beta_next / dbeta_next are Python floats (float64).  Every operand on one device, contiguous, of the
+    stated type, or it is refused before the launch."""
+    cur = st["cur"]
+    device = cur.device
+    B, C, nz = cur.shape
+    rows = B * C
+    ops = dict(st, rec=rec, dz=dz, u=u, mom_next=mom_next, mu0=mu0, lv0=lv0, dh_out=dh_out, flag_out=flag_out,
+               logw_out_next=logw_out_next, keep_out=keep_out)
+    for name, t in ops.items():
+        if t is None:
+            continue
+        if t.device != device:
+            raise _lib.LvaeError("hmc_leap: %s is on %s, cur on %s" % (name, t.device, device))
+        want = (torch.int32 if name in ("accepts", "flag_out") else torch.float64 if name in ("logw", "logw_out_next")
+                else torch.float32)
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError("hmc_leap: %s must be a contiguous %s tensor" % (name, want))
+        n = rows * nz if name in ("pos", "mom", "cur", "d_cur", "mom_next", "keep_out") else B * nz if name in ("mu0", "lv0") else rows
+        if name != "dz" and t.numel() != n:
+            raise ValueError("hmc_leap: %s has %d elements, %d expected for cur %s" % (name, t.numel(), n, tuple(cur.shape)))
+    if dz.numel() == 0 or dz.numel() % (rows * nz) != 0 or (mu0 is None) != (lv0 is None) or (mode == HMC_LAST and u is None):
+        raise ValueError("hmc_leap: operand shapes do not match cur %s" % (tuple(cur.shape),))
+    lib, s = backend_for(device), stream_ptr(device)
+    lib.lv_hmc_leap_f32(P(rec), P(dz), dz.numel() // (rows * nz), P(st["pos"]), P(st["mom"]), P(st["k0"]), P(cur), P(st["g_cur"]),
+                        P(st["lq_cur"]), P(st["rec_cur"]), P(st["d_cur"]), P(st["logw"]), P(st["accepts"]), P(st["eps"]), P(u),
+                        P(mom_next), float(beta), float(beta_next), float(dbeta_next), P(mu0), P(lv0), rows, C, nz, int(L), int(mode),
+                        float(up), float(down), float(eps_min), float(eps_max), P(dh_out), P(flag_out), P(logw_out_next),
+                        P(keep_out), s)
+
+
+def hmc_chain(score, pos, draw, beta, L, step_size, adapt, mu0, lv0, keep=None, iters_per_launch=64):
+    """The loop of the contract (csrc/lv_hmc.hip) around any scorer.  pos [B][C][nz] float32 is the buffer the scorer reads its z
+    from: score() -> (rec [B*C], dz [parts][B*C][nz], parts) at the current pos -- the first call also puts z_0 there -- and the
+    launches rewrite it in place.  draw(i0, n) -> (mom [n][B][C][nz], u [n][B][C]) hands over the noise of transitions i0 ..
+    i0 + n - 1, asked for in chunks of iters_per_launch; beta: N + 1 Python floats; L leapfrog steps per transition; step_size:
+    every chain's starting eps; adapt: None (eps fixed) or (up, down, eps_min, eps_max[, until]) -- adapted after each of the
+    first `until` transitions (default: all); mu0 / lv0 [B][nz] or None (q0 = the prior); keep: None or (burn_in, thin,
+    nsamples) -- cur after transition burn_in + k * thin is sample k.  1 + N * L calls of score(), one lv_hmc_leap_f32 launch
+    after each, nothing read back.
+    -> dict(logw [B][C] f64, cur [B][C][nz], g, lq, step_size [B][C], accepts [B][C] int32, ratios (dH) / flags / logw_trace
+    [N][B][C], samples [B][nsamples][C][nz] or None)."""
+    dev = pos.device
+    B, C, nz = pos.shape
+    N, L, per = len(beta) - 1, int(L), int(iters_per_launch)
+    if N < 1 or L < 1 or per < 1:
+        raise ValueError("hmc_chain: at least one transition, leapfrog >= 1 and iters_per_launch >= 1 expected")
+    f32, i32, f64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.float64))
+    st = {"pos": pos, "mom": torch.zeros(B, C, nz, **f32), "cur": torch.zeros(B, C, nz, **f32), "d_cur": torch.zeros(B, C, nz, **f32)}
+    for k in ("k0", "g_cur", "lq_cur", "rec_cur"):
+        st[k] = torch.zeros(B, C, **f32)
+    st["eps"] = torch.full((B, C), float(step_size), **f32)
+    st["logw"], st["accepts"] = torch.zeros(B, C, **f64), torch.zeros(B, C, **i32)
+    ratios, flags, trace = torch.empty(N, B, C, **f32), torch.empty(N, B, C, **i32), torch.empty(N, B, C, **f64)
+    kept = None
+    if keep is not None:
+        burn_in, thin, nsamples = keep
+        kept = torch.empty(nsamples, B, C, nz, **f32)
+    fixed = dict(up=1.0, down=1.0, eps_min=0.0, eps_max=float("inf"))
+    tuned, until = fixed, 0
+    if adapt is not None:
+        tuned = dict(up=adapt[0], down=adapt[1], eps_min=adapt[2], eps_max=adapt[3])
+        until = N if len(adapt) < 5 else int(adapt[4])
+
+    def chunk(c0):
+        m, u = draw(c0, min(per, N - c0))
+        _same_device("hmc_chain", dev, mom=m, u=u)
+        return m.float().contiguous(), u.float().contiguous()
+    mom, u = chunk(0)
+    c0 = 0                                                        # first transition of the chunk (mom, u) covers
+    rec, dz, _ = score()
+    hmc_leap(rec, dz, st, HMC_INIT, L, mom_next=mom[0], beta_next=beta[1], dbeta_next=beta[1] - beta[0], mu0=mu0, lv0=lv0,
+             logw_out_next=trace[0])
+    for it in range(N):                                           # transition it + 1 of the contract, at beta[it + 1]
+        for _ in range(L - 1):
+            rec, dz, _ = score()
+            hmc_leap(rec, dz, st, HMC_MID, L, beta=beta[it + 1], mu0=mu0, lv0=lv0)
+        rec, dz, _ = score()
+        u_it = u[it - c0]
+        more = it + 1 < N
+        if more and it + 1 - c0 >= mom.shape[0]:
+            c0 = it + 1
+            mom, u = chunk(c0)
+        k = -1
+        if keep is not None and it >= burn_in and (it - burn_in) % thin == 0 and (it - burn_in) // thin < nsamples:
+            k = (it - burn_in) // thin
+        hmc_leap(rec, dz, st, HMC_LAST, L, u=u_it, mom_next=mom[it + 1 - c0] if more else None, beta=beta[it + 1],
+                 beta_next=beta[it + 2] if more else 0.0, dbeta_next=beta[it + 2] - beta[it + 1] if more else 0.0, mu0=mu0, lv0=lv0,
+                 dh_out=ratios[it], flag_out=flags[it], logw_out_next=trace[it + 1] if more else None,
+                 keep_out=kept[k] if k >= 0 else None, **(tuned if it < until else fixed))
+    return {"logw": st["logw"], "cur": st["cur"], "g": st["g_cur"], "lq": st["lq_cur"], "step_size": st["eps"],
+            "accepts": st["accepts"], "ratios": ratios, "flags": flags, "logw_trace": trace,
+            "samples": None if kept is None else kept.permute(1, 0, 2, 3).contiguous()}
 
 
 def calc_mi(mu, logvar, z):

@@ -60,12 +60,21 @@ def calc_iwnll(model, test_data_batch, args, ns=100, verbose=False, np_rng=None)
     return nll, ppl
 
 
+def _ais_defaults(args, ais_kwargs):
+    """The proposal scale nll_ais has no built-in value for, from `args`: std = args.ais_std for random-walk transitions,
+    step_size = args.ais_step_size for transition="hmc" (which refuses std)."""
+    key, field = ("step_size", "ais_step_size") if ais_kwargs.get("transition", "rw") == "hmc" else ("std", "ais_std")
+    if key not in ais_kwargs and hasattr(args, field):
+        ais_kwargs = dict(ais_kwargs, **{key: getattr(args, field)})
+    return ais_kwargs
+
+
 def calc_aisnll(model, test_data_batch, args, np_rng=None, verbose=False, **ais_kwargs):
     """calc_iwnll's bookkeeping over VAE.nll_ais (annealed importance sampling: an estimate of log p(x) that does not lean on
-    the encoder).  ais_kwargs go to nll_ais (chains, temps, transitions, std, schedule, init, generator, ...); std defaults to
-    args.ais_std as nll_ais reads it from model.args.  Returns (nll, ppl)."""
-    if "std" not in ais_kwargs and hasattr(args, "ais_std"):
-        ais_kwargs = dict(ais_kwargs, std=args.ais_std)
+    the encoder).  ais_kwargs go to nll_ais (chains, temps, transitions, std, schedule, init, generator, transition, leapfrog,
+    step_size, adapt, ...); std defaults to args.ais_std (step_size to args.ais_step_size for transition="hmc") as nll_ais reads
+    it from model.args.  Returns (nll, ppl)."""
+    ais_kwargs = _ais_defaults(args, ais_kwargs)
     tot = []
     report_num_words = report_num_sents = 0
     for i in (np_rng if np_rng is not None else np.random).permutation(len(test_data_batch)):
@@ -236,8 +245,7 @@ def image_calc_iwnll(model, test_loader, args, verbose=False):
 
 def image_calc_aisnll(model, test_loader, args, verbose=False, **ais_kwargs):
     """calc_aisnll over one pass of a loader of (batch, label) pairs, per example (the step route: PixelCNN decoder)."""
-    if "std" not in ais_kwargs and hasattr(args, "ais_std"):
-        ais_kwargs = dict(ais_kwargs, std=args.ais_std)
+    ais_kwargs = _ais_defaults(args, ais_kwargs)
     tot = []
     report_num_examples = 0
     for batch_data, _ in test_loader:

@@ -4,6 +4,7 @@
 encoder / reparam+KL / decoder autograd Functions.  The evaluation helpers keep the reference's method names and
 semantics on top of the same HIP forward (nll_iw, eval_*, calc_mi_q: SURVEY.md 8f "next" rows).
 """
+import contextlib
 import math
 
 import torch
@@ -275,7 +276,8 @@ class VAE(nn.Module):
         return eng.cond_ll_supported(x.size(1))
 
     def sample_from_posterior(self, x, nsamples, chains=1, burn_in=None, thin=None, std=None, noise=None, generator=None,
-                              iters_per_launch=None, return_info=False):
+                              iters_per_launch=None, return_info=False, transition="rw", leapfrog=10, step_size=None, adapt=None,
+                              step_bounds=(1e-4, 0.5)):
         """Random-walk Metropolis-Hastings samples from the model posterior p(z|x) (reference vae.py:218-254)
         -> (batch, nsamples, chains, nz) float32 on x's device, computed under torch.no_grad().
 
@@ -305,20 +307,41 @@ class VAE(nn.Module):
         Neither reads anything back to the host inside the chain.
 
         return_info: also {"accept_rate": [B, chains], "log_joint": [B, chains] (the final cur_ll), "route", "iterations",
-        "ratios": [iterations, B, chains], "accepts": [iterations, B, chains] (the per-iteration ratio and accept flag)}."""
+        "ratios": [iterations, B, chains], "accepts": [iterations, B, chains] (the per-iteration ratio and accept flag)}.
+
+        transition="hmc": every iteration is a Hamiltonian transition on p(z, x) -- nll_ais's session (csrc/lv_hmc.hip, DESIGN.md
+        3.1.3) with the prior as q0 and beta = 1 throughout: `leapfrog` steps of size step_size (default args.mh_step_size), std
+        not passed, noise = (z0, mom [iterations][B][chains][nz], u).  adapt = (target, rate) adapts the step size during burn_in
+        only, so the kept samples come from a fixed kernel.  Routes "hmc-fused" / "hmc-generic" as nll_ais has them; "ratios"
+        holds dH; variable-length pairs are refused."""
         a = self.args
+        if transition not in ("rw", "hmc"):
+            raise ValueError("sample_from_posterior: transition 'rw' or 'hmc' expected, got %r" % (transition,))
+        if transition == "hmc" and std is not None:
+            raise ValueError("sample_from_posterior: std is the random-walk proposal scale; transition='hmc' takes step_size")
         vals = [burn_in, thin, std]
-        for i, f in enumerate(("mh_burn_in", "mh_thin", "mh_std")):
+        for i, f in enumerate(("mh_burn_in", "mh_thin", "mh_std")[:2 if transition == "hmc" else 3]):
             if vals[i] is None:
                 if not hasattr(a, f):
                     raise ValueError("sample_from_posterior: pass burn_in / thin / std or set args.mh_burn_in, args.mh_thin "
                                      "and args.mh_std (missing: %s)" % f)
                 vals[i] = getattr(a, f)
-        burn_in, thin, std = int(vals[0]), int(vals[1]), float(vals[2])
+        burn_in, thin = int(vals[0]), int(vals[1])
         nsamples, chains = int(nsamples), int(chains)
         if nsamples < 1 or chains < 1 or burn_in < 0 or thin < 1:
             raise ValueError("sample_from_posterior: nsamples >= 1, chains >= 1, burn_in >= 0, thin >= 1 expected")
         total = burn_in + nsamples * thin
+        if transition == "hmc":
+            L, step_size, adapt = self._hmc_arguments("sample_from_posterior", "mh_step_size", leapfrog, step_size, adapt, step_bounds)
+            if adapt is not None:
+                adapt = adapt + (burn_in,)
+            r, route = self._hmc_run("sample_from_posterior", x, chains, [1.0] * (total + 1), "sampler", noise, generator, L,
+                                     step_size, adapt, (burn_in, thin, nsamples), iters_per_launch)
+            if not return_info:
+                return r["samples"]
+            return r["samples"], {"accept_rate": r["accepts"].float() / float(total), "log_joint": r["lq"] + r["g"], "route": route,
+                                  "iterations": total, "ratios": r["ratios"], "accepts": r["flags"]}
+        std = float(vals[2])
         x = self._batch(x)
         with torch.no_grad():
             dev = x.device if torch.is_tensor(x) else x[0].device
@@ -434,7 +457,8 @@ class VAE(nn.Module):
         return [b[0]] + [v for v in b[1:] for _ in range(transitions)]
 
     def nll_ais(self, x, chains=16, temps=500, transitions=1, std=None, schedule="sigmoid", init="prior", noise=None,
-                generator=None, iters_per_launch=None, return_info=False):
+                generator=None, iters_per_launch=None, return_info=False, transition="rw", leapfrog=10, step_size=None, adapt=None,
+                step_bounds=(1e-4, 0.5)):
         """Annealed importance sampling estimate of -log p(x) (Neal 2001; Wu et al. 2017) -> (batch,) float32 on x's device,
         computed under torch.no_grad().  Unlike nll_iw the estimate does not lean on the encoder: `chains` chains per sentence
         start at a draw from q0 -- the prior (init="prior") or q(z|x) (init="encoder") -- and move through N = temps *
@@ -457,7 +481,23 @@ class VAE(nn.Module):
 
         return_info: also {"logw": [B, chains] float64, "accept_rate": [B, chains], "accept_rate_iter": [N], "route",
         "iterations", "se": [B] (the delta-method standard error of log p^: sqrt(var_c(w_c / mean w) / chains); nan for one
-        chain), "ratios" / "accepts" / "logw_trace": [N, B, chains]}."""
+        chain), "ratios" / "accepts" / "logw_trace": [N, B, chains]}.
+
+        transition="hmc": the N transitions are Hamiltonian (Wu et al. 2017; Cremer et al. 2018) -- `leapfrog` = L leapfrog steps
+        of size step_size on U_beta = -log q0 - beta g with a fresh N(0, I) momentum, then a Metropolis decision on the
+        Hamiltonian; the contract is at the top of csrc/lv_hmc.hip, DESIGN.md 3.1.3.  A transition costs L decoder forwards and
+        backwards to z on all batch * chains rows (1 + N L passes in all), with the decoder in eval arithmetic whatever `training`
+        says.  std must not be passed.  step_size: default args.ais_step_size; there is no built-in value, as for std.  adapt =
+        (target, rate), e.g. (0.65, 0.02): after every transition a chain's step size is multiplied by exp(rate (1 - target)) if it
+        accepted and by exp(-rate target) if not (both rounded to float32, so it is stationary at acceptance = target), and
+        clamped to step_bounds; None keeps it fixed.  noise = (z0 [B][chains][nz], mom [N][B][chains][nz], u [N][B][chains]).
+        Variable-length pairs are refused.  Nothing of the model changes (refine_posterior's guarantee), and with `noise` given no
+        RNG state does.  Routes (class switch fused_hmc = False forces the second):
+          "hmc-fused":   LSTM decoder, batch * chains rows inside svi_supported -- engine.LSTMDecoderEngine.hmc_ais;
+          "hmc-generic": everything else -- decoder.reconstruct_error and torch.autograd.grad for d rec / d z (weight gradients
+                         land in scratch that is restored afterwards), lv_hmc_leap_f32 for the rest.
+        info then also has "step_size" [B, chains] (the final one), "leapfrog" and "cur" [B, chains, nz] (the chains' final
+        states); "ratios" holds dH."""
         chains = int(chains)
         if chains < 1:
             raise ValueError("nll_ais: chains >= 1 expected")
@@ -465,6 +505,15 @@ class VAE(nn.Module):
         total = len(beta) - 1
         if init not in ("prior", "encoder"):
             raise ValueError("nll_ais: init 'prior' or 'encoder' expected, got %r" % (init,))
+        if transition not in ("rw", "hmc"):
+            raise ValueError("nll_ais: transition 'rw' or 'hmc' expected, got %r" % (transition,))
+        if transition == "hmc":
+            if std is not None:
+                raise ValueError("nll_ais: std is the random-walk proposal scale; transition='hmc' takes step_size")
+            L, step_size, adapt = self._hmc_arguments("nll_ais", "ais_step_size", leapfrog, step_size, adapt, step_bounds)
+            r, route = self._hmc_run("nll_ais", x, chains, beta, init, noise, generator, L, step_size, adapt, None, iters_per_launch)
+            return self._ais_estimate(r, chains, total, route, beta, return_info, {"step_size": r["step_size"], "leapfrog": L,
+                                                                                         "cur": r["cur"]})
         if std is None:
             if not hasattr(self.args, "ais_std"):
                 raise ValueError("nll_ais: pass std or set args.ais_std (there is no default proposal scale)")
@@ -515,6 +564,12 @@ class VAE(nn.Module):
             else:
                 route = "step"
                 r = self._ais_by_steps(x, z0, draw, beta, stds, mu0, lv0, iters_per_launch)
+        return self._ais_estimate(r, chains, total, route, beta, return_info, {"std": stds})
+
+    @staticmethod
+    def _ais_estimate(r, chains, total, route, beta, return_info, extra):
+        """The float64 epilogue of nll_ais on a finished set of chains: log p^(x) = logsumexp_c logw_c - log chains."""
+        with torch.no_grad():
             logw = r["logw"]
             log_px = torch.logsumexp(logw, dim=1) - math.log(chains)
             nll = (-log_px).float()
@@ -524,9 +579,9 @@ class VAE(nn.Module):
             w = w / w.mean(dim=1, keepdim=True)
             se = torch.sqrt(w.var(dim=1, unbiased=True) / chains) if chains > 1 else torch.full_like(log_px, float("nan"))
             flags = r["flags"]
-        return nll, {"logw": logw, "accept_rate": r["accepts"].float() / float(total),
-                     "accept_rate_iter": flags.float().mean(dim=(1, 2)), "route": route, "iterations": total, "se": se,
-                     "ratios": r["ratios"], "accepts": flags, "logw_trace": r["logw_trace"], "beta": beta, "std": stds}
+        return nll, dict({"logw": logw, "accept_rate": r["accepts"].float() / float(total),
+                          "accept_rate_iter": flags.float().mean(dim=(1, 2)), "route": route, "iterations": total, "se": se,
+                          "ratios": r["ratios"], "accepts": flags, "logw_trace": r["logw_trace"], "beta": beta}, **extra)
 
     def _ais_by_steps(self, x, z0, draw, beta, stds, mu0, lv0, iters_per_launch):
         """Route "step" of nll_ais: eval_cond_ll for the scores, lv_ais_step_f32 for everything else.  The launch that decides
@@ -565,6 +620,130 @@ class VAE(nn.Module):
                           stds[it + 1] if more else 0.0, beta[it + 2] - beta[it + 1] if more else 0.0, mu0, lv0,
                           ratio_out=ratios[it], flag_out=flags[it], logw_out_next=trace[it + 1] if more else None)
         return {"logw": logw, "cur": cur, "g": g, "accepts": accepts, "ratios": ratios, "flags": flags, "logw_trace": trace}
+
+    # True: transition="hmc" takes the decoder engine's session (LSTMDecoderEngine.hmc_ais) where _fused_hmc_ok allows it; False
+    # forces the generic route (A/B runs, tests, the bench baseline)
+    fused_hmc = True
+
+    def _fused_hmc_ok(self, x, B, C):
+        """Route "hmc-fused", in the style of _fused_svi_ok: an LSTM decoder, x a 2-D int64 tensor on a device the package has
+        kernels for, B * C decoder rows inside the session's envelope."""
+        eng = getattr(self.decoder, "_hip", None)
+        if not (self.fused_hmc and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.int64):
+            return False
+        try:
+            eng.ensure(x.device)
+        except _lib.LvaeError:
+            return False
+        return eng.svi_supported(B, C)
+
+    def _hmc_arguments(self, who, field, leapfrog, step_size, adapt, step_bounds):
+        """-> (L, step_size, None or (up, down, eps_min, eps_max)) or ValueError; up / down are rounded to float32 here, as the
+        kernel receives them."""
+        L = int(leapfrog)
+        if L < 1:
+            raise ValueError("%s: leapfrog >= 1 expected" % who)
+        if step_size is None:
+            if not hasattr(self.args, field):
+                raise ValueError("%s: pass step_size or set args.%s (there is no default step size)" % (who, field))
+            step_size = getattr(self.args, field)
+        step_size = float(step_size)
+        lo, hi = (float(v) for v in step_bounds)
+        if not (0.0 < step_size < float("inf")) or not (0.0 < lo <= hi < float("inf")):
+            raise ValueError("%s: step_size > 0 and step_bounds 0 < min <= max expected" % who)
+        if adapt is None:
+            return L, step_size, None
+        target, rate = (float(v) for v in adapt)
+        if not (0.0 < target < 1.0 and 0.0 < rate < float("inf")):
+            raise ValueError("%s: adapt = (target in (0, 1), rate > 0) expected" % who)
+        up, down = (float(torch.tensor(math.exp(v), dtype=torch.float32)) for v in (rate * (1.0 - target), -rate * target))
+        return L, step_size, (up, down, lo, hi)
+
+    def _hmc_run(self, who, x, chains, beta, init, noise, generator, L, step_size, adapt, keep, iters_per_launch):
+        """The Hamiltonian chains of nll_ais (init "prior" / "encoder") and sample_from_posterior (init "sampler": z_0 from the
+        encoder, q0 the prior) -> (engine.hmc_chain's result, route).  Every refusal comes before anything is launched; the
+        decoder runs in eval arithmetic and the training flags are restored."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("%s: transition='hmc' does not take variable-length batches (x, lengths); batch by length" % who)
+        if iters_per_launch is not None and int(iters_per_launch) < 1:
+            raise ValueError("%s: iters_per_launch >= 1 expected" % who)
+        B, dev, nz, total = x.size(0), x.device, self.nz, len(beta) - 1
+        if noise is not None:
+            z0, mom_all, u_all = noise
+            for name, t in (("z0", z0), ("mom", mom_all), ("u", u_all)):
+                if t.device != dev:              # the kernels take raw pointers: refused before anything is launched
+                    raise _lib.LvaeError("%s: %s is on %s, x on %s" % (who, name, t.device, dev))
+            if (tuple(z0.shape) != (B, chains, nz) or tuple(mom_all.shape) != (total, B, chains, nz)
+                    or tuple(u_all.shape) != (total, B, chains)):
+                raise ValueError("%s: noise z0 [%d][%d][%d], mom [%d][%d][%d][%d], u [%d][%d][%d] expected, got %s, %s, %s"
+                                 % (who, B, chains, nz, total, B, chains, nz, total, B, chains, tuple(z0.shape),
+                                    tuple(mom_all.shape), tuple(u_all.shape)))
+        flags = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            with torch.no_grad():
+                mu0 = lv0 = None
+                if init == "encoder":
+                    if noise is None:
+                        z0, (mu0, lv0) = self.encoder.sample(x, chains)
+                    else:
+                        mu0, lv0 = self.encode_stats(x)
+                    mu0, lv0 = mu0.detach().float().contiguous(), lv0.detach().float().contiguous()
+                elif noise is None:
+                    z0 = (self.encoder.sample(x, chains)[0] if init == "sampler"
+                          else torch.randn(B, chains, nz, device=dev, generator=generator))
+                z0 = z0.detach().float().contiguous()
+
+                def draw(i0, n):
+                    if noise is not None:
+                        return mom_all[i0:i0 + n], u_all[i0:i0 + n]
+                    return (torch.randn(n, B, chains, nz, device=dev, generator=generator),
+                            torch.rand(n, B, chains, device=dev, generator=generator))
+                if self._fused_hmc_ok(x, B, chains):
+                    return self.decoder._hip.hmc_ais(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch), "hmc-fused"
+                return self._hmc_generic(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch), "hmc-generic"
+        finally:
+            for m, t in flags:
+                m.training = t
+
+    def _hmc_generic(self, x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch):
+        """Route "hmc-generic": rec and d rec / d z from what every decoder has -- reconstruct_error and its autograd backward, as
+        _svi_generic gets them -- and lv_hmc_leap_f32 (one plain gradient: parts = 1) for everything else."""
+        if iters_per_launch is None:
+            T = x.size(1) if x.dim() == 2 else 33
+            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
+        pos = z0.clone()
+
+        def score():
+            with torch.enable_grad():
+                z = pos.detach().requires_grad_(True)
+                rec = self.decoder.reconstruct_error(x, z)
+                dz = torch.autograd.grad(rec, z, torch.ones_like(rec))[0]
+            return rec.detach().float().reshape(-1).contiguous(), dz.float().contiguous(), 1
+        with self._decoder_gradients_preserved(z0.device):
+            return _eng.hmc_chain(score, pos, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch)
+
+    @contextlib.contextmanager
+    def _decoder_gradients_preserved(self, dev):
+        """A decoder backward under torch autograd leaves weight gradients as by-products: the engine's flat gradient buffers are
+        saved before and restored after, and the parameters' .grad are put back (torch.autograd.grad asks for dz only)."""
+        eng = getattr(self.decoder, "_hip", None)
+        if hasattr(eng, "ensure"):
+            eng.ensure(dev)
+        flat = getattr(eng, "flat", None)
+        grads = [(p, p.grad) for p in self.decoder.parameters()]
+        saved = [s[0].clone() for s in flat._slots] if flat is not None else None
+        detached = getattr(flat, "detached", None)
+        try:
+            yield
+        finally:
+            if saved is not None:
+                for slot, keep_ in zip(flat._slots, saved):
+                    slot[0].copy_(keep_)
+                flat.detached = detached
+            for p, g0 in grads:
+                p.grad = g0
 
     # True: refine_posterior takes the engine's refinement session (lv_svi_step_f32, lv_dec_tail_dz_f32) where _fused_svi_ok
     # allows it; False forces the generic route (A/B runs, the tests' second oracle, the bench baseline)
@@ -662,13 +841,6 @@ class VAE(nn.Module):
         (torch.autograd.grad asks for dz only)."""
         B, ns = eps.shape[0], eps.shape[1]
         dev = mulv0.device
-        eng = getattr(self.decoder, "_hip", None)
-        if hasattr(eng, "ensure"):
-            eng.ensure(dev)
-        flat = getattr(eng, "flat", None)
-        grads = [(p, p.grad) for p in self.decoder.parameters()]
-        saved = [s[0].clone() for s in flat._slots] if flat is not None else None
-        detached = getattr(flat, "detached", None)
         phi = mulv0.clone()
         vel = torch.zeros_like(phi)
         best = phi.clone()
@@ -676,7 +848,7 @@ class VAE(nn.Module):
         trace = torch.empty(steps + 1, B, dtype=torch.float32, device=dev)
         rec_trace, kl_trace = torch.empty_like(trace), torch.empty_like(trace)
         dkl = torch.full((B,), kl_weight, dtype=torch.float32, device=dev)
-        try:
+        with self._decoder_gradients_preserved(dev):
             for k in range(steps + 1):
                 z, kl = _eng.reparam_kl_forward(phi, eps)
                 with torch.enable_grad():
@@ -695,13 +867,6 @@ class VAE(nn.Module):
                 g = g * torch.clamp(clip / (g.norm(dim=1, keepdim=True) + 1e-6), max=1.0)
                 vel = momentum * vel + g
                 phi = phi - lr * vel
-        finally:
-            if saved is not None:
-                for slot, keep_ in zip(flat._slots, saved):
-                    slot[0].copy_(keep_)
-                flat.detached = detached
-            for p, g0 in grads:
-                p.grad = g0
         return {"last": phi, "best": best, "best_loss": best_loss, "trace": trace, "rec_trace": rec_trace, "kl_trace": kl_trace}
 
     def calc_infer_mean(self, x):
