@@ -429,6 +429,28 @@ int lv_svi_step_f32(const float* rec, const float* dz, int dz_parts, const float
                     float* best_mulv, float* best_loss, float* trace_row, float* z_next, float* kl_next, int B, int ns,
                     int nz, void* stream);
 
+/* ---- semi-amortized training: the backward pass through the K refinement steps (lv_savae.hip; SA-VAE, Kim et al. 2018) ------
+ * lv_svi_rec_step_f32: lv_svi_step_f32's update without the loss record and the best-iterate tracking; it also stores the
+ * unclipped gradient g_k and the iterate lambda_k (before the update) into g_rec, phi_rec [B][2nz], step k's rows of the
+ * [K][B][2nz] records.  mulv, vel, z_next, kl_next: bit-equal to lv_svi_step_f32 on the same inputs.
+ * lv_savae_adjoint_f32, one launch (one workgroup) per backward iteration k = K-1 .. 0, with lbar / vbar the adjoints of lambda / v:
+ *   vb = vbar - lr*lbar;  per sentence r = |g|_2, s = clip/(r + 1e-6):  gb = vb where s >= 1, else
+ *   gb = s*vb - clip*(g.vb)/(r*(r + 1e-6)^2)*g;  vbar = momentum*vb;  n = |gb|_2 over all B*2nz entries (summed in double);
+ *   e = fd_eps*max(1, max|lam|);  c = n/(2e);  scal = (n, e, c);  u = gb/n (n = 0: u = 0, c = 0);
+ *   z_pm [B][2ns][nz]: samples 0..ns-1 (mu + e*u_mu) + eps_s*exp((logvar + e*u_lv)/2), samples ns..2ns-1 the same at -e;
+ *   seeds [B*2ns]: +c/ns on the first ns rows of a sentence, -c/ns on the others.
+ * lv_savae_hvp_f32: from dz [dz_parts][B*2ns][nz] of the decoder pass at z_pm seeded with `seeds`,
+ *   lbar += c*(grad_lambda F(lam + e*u) - grad_lambda F(lam - e*u)),  F = sum_b L_b,  beta = kl_weight_dev[0];
+ *   the reparameterisation chain rule and the analytic-KL terms are evaluated at the perturbed points.  n = 0: lbar untouched. */
+int lv_svi_rec_step_f32(const float* dz, int dz_parts, const float* eps, const float* kl_weight_dev, float lr, float momentum,
+                        float clip, float* mulv, float* vel, float* g_rec, float* phi_rec, float* z_next, float* kl_next, int B,
+                        int ns, int nz, void* stream);
+int lv_savae_adjoint_f32(const float* lbar, float* vbar, const float* g, const float* lam, const float* eps, float lr,
+                         float momentum, float clip, float fd_eps, float* u, float* scal, float* z_pm, float* seeds, int B, int ns,
+                         int nz, void* stream);
+int lv_savae_hvp_f32(const float* dz, int dz_parts, const float* eps, const float* lam, const float* u, const float* scal,
+                     const float* kl_weight_dev, float* lbar, int B, int ns, int nz, void* stream);
+
 /* small elementwise / reductions used by the sequencing (h0 = tanh(c0) dec_lstm.py:100; bias grads) */
 int lv_tanh_f32(const float* in, float* out, long n, void* stream);
 int lv_colsum_f32(const float* in, long ld, int R, int C, float* out, float* out2, void* stream);

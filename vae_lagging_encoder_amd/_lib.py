@@ -69,6 +69,9 @@ SIGNATURES = {
     "lv_dec_tail_bwd_f32": [_vp, _vp, _vp, _vp, _l, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_dec_tail_dz_f32": [_vp, _vp, _vp, _l, _i, _vp, _vp, _i, _i, _i, _vp],
     "lv_svi_step_f32": [_vp, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_svi_rec_step_f32": [_vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_savae_adjoint_f32": [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_savae_hvp_f32": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_clip_norm2_f32": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp],
     "lv_clip_norm2_txn_f32": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lv_clip_norm2_fold_txn_f32": [_vp, _l, _vp, _l, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

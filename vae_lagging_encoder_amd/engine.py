@@ -2053,9 +2053,10 @@ class LSTMDecoderEngine(object):
 
     # A frozen-decoder pass at the z in sv.z, shared by svi_refine and hmc_ais: _zpass_begin once per call, then per pass
     # _zpass_forward (leaves w.rec) and _zpass_dz (the gradient of sum_row sv.rowscale[row] * rec[row] with respect to z).
-    def _zpass_begin(self, x, ns, w, sv):
-        """Exact f32: the z-independent work -- embedding gather, the word half of the input projection (sv.Gxw), the targets in
-        decoder row order.  -> the token ids the per-row kernels read.  bf16: nothing (forward() repeats its own)."""
+    def _zpass_begin(self, x, ns, w, sv, mask_in=None, sc_in=1.0):
+        """Exact f32: the z-independent work -- embedding gather (mask_in: dropout_in's keep-mask [B][T-1][ni], savae_forward's
+        training arithmetic), the word half of the input projection (sv.Gxw), the targets in decoder row order.  -> the token ids the
+        per-row kernels read.  bf16: nothing (forward() repeats its own)."""
         if self.precision != "f32":
             return x
         B, T = x.shape
@@ -2064,7 +2065,7 @@ class LSTMDecoderEngine(object):
         V, ni, H, nz = self.dims()
         v = self.flat.views
         ids = x
-        lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, None, 1.0, P(w.X), Td, B, ni, V, s)
+        lib.lv_embed_gather_f32(P(v["embed.weight"]), P(x), T, P(mask_in), sc_in, P(w.X), Td, B, ni, V, s)
         _gemm(lib, s, 0, 1, Td * B, 4 * H, ni, P(w.X), ni, P(v["lstm.weight_ih_l0"]), ni + nz, P(sv.Gxw), 4 * H, prec=self.precision)
         if ns > 1:
             lib.lv_repeat_rows_i64(P(x), P(w.x_rep), B, T, ns, s)
@@ -2073,7 +2074,8 @@ class LSTMDecoderEngine(object):
         self.last_steps = None                         # equal-length BPTT, whatever the last forward() was given
         return ids
 
-    def _zpass_forward(self, x, ids, ns, w, sv):
+    def _zpass_forward(self, x, ids, ns, w, sv, mask_out=None, sc_out=1.0):
+        """mask_out: dropout_out's keep-mask [B*ns][T-1][H] (exact f32 only), as forward()'s."""
         B, T = x.shape
         V, ni, H, nz = self.dims()
         if self.precision != "f32":
@@ -2085,12 +2087,12 @@ class LSTMDecoderEngine(object):
         lib.lv_dec_init_f32(P(sv.z), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]), ni + nz, ni, P(v["lstm.bias_ih_l0"]),
                             P(v["lstm.bias_hh_l0"]), P(w.cs), P(w.hs), P(w.Zp), 0, Bd, H, nz, s)
         lib.lv_gx_expand_add_f32(P(sv.Gxw), P(w.Zp), P(w.Gx), Td, B, ns, 4 * H, s)
-        _lstm_forward(self, lib, s, None, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), None, 1.0, P(w.O), Td, Bd, H, x.device)
+        _lstm_forward(self, lib, s, None, w, P(w.Gx), P(v["lstm.weight_hh_l0"]), P(mask_out), sc_out, P(w.O), Td, Bd, H, x.device)
         _gemm(lib, s, 0, 1, Td * Bd, V, H, P(w.O), H, P(v["pred_linear.weight"]), H, P(w.logits), w.ldl, prec=self.precision)
         lib.lv_softmax_nll_fwd_f32(P(w.logits), w.ldl, P(ids), T, 1, P(w.lse), P(w.nll), Td, Bd, V, s)
         lib.lv_vae_loss_f32(P(w.nll), P(w.klz), P(w.zero1), P(w.loss), P(w.rec), Td, Bd, s)
 
-    def _zpass_dz(self, x, ids, ns, w, sv):
+    def _zpass_dz(self, x, ids, ns, w, sv, mask_out=None, sc_out=1.0):
         """-> (the dz tail's partial sums [parts][B*ns][nz], parts)"""
         if self.precision != "f32":
             return self.backward_dz(sv.rowscale, partial_dz=True)
@@ -2099,7 +2101,7 @@ class LSTMDecoderEngine(object):
         lib, s = self.lib, stream_ptr(x.device)
         V, ni, H, nz = self.dims()
         self._bwd_dlogits(lib, s, w, None, ids, sv.rowscale, T, Td, Bd, V)
-        self._bwd_dO_bptt(lib, s, w, None, None, None, 1.0, Td, Bd, V, H, x.device)
+        self._bwd_dO_bptt(lib, s, w, None, None, mask_out, sc_out, Td, Bd, V, H, x.device)
         return self._bwd_tail_dz(lib, s, w, Bd, H, ni, nz, True)
 
     def svi_refine(self, x, mulv, eps, steps, lr, momentum, clip, kl_weight):
@@ -2157,6 +2159,118 @@ class LSTMDecoderEngine(object):
             kl, kl_next = kl_next, kl
         self.gen += 1                                  # the workspaces no longer hold what the last forward() left
         return {"last": phi, "best": best, "best_loss": best_loss, "trace": trace, "rec_trace": rec_trace, "kl_trace": kl_trace}
+
+    # ---- semi-amortized training (VAE.loss_savae / trainer.SemiAmortizedTextTrainer) ---------------------------------
+    def savae_supported(self, B, ns):
+        """The semi-amortized step's envelope: exact f32, and the decoder's batch-sized ends (lv_dec_init_f32 / lv_dec_tail_*) on the
+        largest row count it uses, the B * 2ns rows of the perturbed pair."""
+        return self.precision == "f32" and fused_ends_ok(B * 2 * ns, self.dims()[3])
+
+    def savae_forward(self, x, mulv, eps, mask_in, mask_out, p_in, p_out, steps, lr, momentum, clip, kl_weight):
+        """The forward half of a semi-amortized step (contract: csrc/lv_savae.hip): `steps` refinement steps from lambda_0 = mulv
+        [B][2nz] in svi_refine's session -- here with the step's dropout keep-masks (mask_in [B][T-1][ni], mask_out [B*ns][T-1][H],
+        uint8, or None), the same in every pass -- recorded by lv_svi_rec_step_f32, then forward() at lambda_K, whose activations
+        savae_backward starts from.  -> the step's record: rec [B] (sample mean) and kl [B] at lambda_K, lam (lambda_K), the
+        [K][B][2nz] records g_rec / lam_rec, rec0 / kl0 (the two terms of L_b(lambda_0)).  Exact f32 only; nothing is read back."""
+        steps = int(steps)
+        x = x.contiguous()
+        B, T = x.shape
+        Td = T - 1
+        dev = x.device
+        _same_device("savae_forward", dev, mulv=mulv, eps=eps, mask_in=mask_in, mask_out=mask_out)
+        self.ensure(dev)
+        if self.precision != "f32":
+            raise _lib.LvaeError("semi-amortized training runs in the exact-f32 configuration only")
+        nz = self.dims()[3]
+        if tuple(mulv.shape) != (B, 2 * nz) or eps.dim() != 3 or eps.shape[0] != B or eps.shape[2] != nz or eps.shape[1] < 1:
+            raise ValueError("savae_forward: mulv [%d][%d] and eps [%d][ns][%d] expected, got %s and %s"
+                             % (B, 2 * nz, B, nz, tuple(mulv.shape), tuple(eps.shape)))
+        ns = int(eps.shape[1])
+        Bd = B * ns
+        lib, s = self.lib, stream_ptr(dev)
+        eps = eps.detach().float().contiguous()
+        sc_in = 1.0 / (1.0 - p_in) if mask_in is not None else 1.0
+        sc_out = 1.0 / (1.0 - p_out) if mask_out is not None else 1.0
+        sv = self._svi_ws(B, ns, Td)
+        f32 = dict(dtype=torch.float32, device=dev)
+        lam = mulv.detach().float().contiguous().clone()
+        st = _NS()
+        st.g_rec, st.lam_rec = torch.empty(steps, B, 2 * nz, **f32), torch.empty(steps, B, 2 * nz, **f32)
+        st.klw = torch.full((1,), float(kl_weight), **f32)
+        st.rec0 = st.kl0 = None
+        if steps > 0:
+            vel = torch.zeros(B, 2 * nz, **f32)
+            sv.rowscale.fill_(1.0 / ns)
+            w = self._ws(Bd, Td, ns)
+            ids = self._zpass_begin(x, ns, w, sv, mask_in, sc_in)
+            kl, kl_next = sv.kl
+            lib.lv_reparam_kl_fwd_f32(P(lam), P(eps), P(sv.z), P(kl), B, ns, nz, s)
+            for k in range(steps):
+                self._zpass_forward(x, ids, ns, w, sv, mask_out, sc_out)
+                if k == 0:
+                    st.rec0, st.kl0 = w.rec.view(B, ns).sum(dim=1).div_(ns), kl.clone()
+                dzp, parts = self._zpass_dz(x, ids, ns, w, sv, mask_out, sc_out)
+                lib.lv_svi_rec_step_f32(P(dzp), parts, P(eps), P(st.klw), float(lr), float(momentum), float(clip), P(lam), P(vel),
+                                        P(st.g_rec, k * B * 2 * nz), P(st.lam_rec, k * B * 2 * nz), P(sv.z), P(kl_next), B, ns, nz, s)
+                kl, kl_next = kl_next, kl
+        st.z, st.kl = reparam_kl_forward(lam, eps)
+        rec_rows = self.forward(x, st.z, mask_in, mask_out, p_in, p_out)
+        st.rec = rec_rows.view(B, ns).sum(dim=1).div_(ns)
+        if steps == 0:
+            st.rec0, st.kl0 = st.rec, st.kl
+        st.gen = self.gen
+        st.x, st.eps, st.lam, st.steps, st.ns = x, eps, lam, steps, ns
+        st.masks = (mask_in, mask_out, p_in, p_out)
+        st.hyper = (float(lr), float(momentum), float(clip))
+        return st
+
+    def savae_backward(self, st, seeds, fd_eps):
+        """The backward half: seeds [B] = d(objective)/d loss_b.  The full backward at lambda_K, then for k = K-1 .. 0
+        lv_savae_adjoint_f32, ONE forward() / backward() on the B * 2ns rows of the perturbed pair (both rows of (b, s) under
+        mask_out's row (b, s)), lv_add_f32 of its weight gradients into the running sum and lv_savae_hvp_f32.  Leaves the decoder's
+        gradient in flat.grad and returns the gradient with respect to lambda_0 [B][2nz] (the encoder backward's dmulv)."""
+        x, eps, ns, K = st.x, st.eps, st.ns, st.steps
+        B, T = x.shape
+        dev = x.device
+        nz = self.dims()[3]
+        lib, s = self.lib, stream_ptr(dev)
+        f = self.flat
+        lr, mom, clip = st.hyper
+        mask_in, mask_out, p_in, p_out = st.masks
+        f32 = dict(dtype=torch.float32, device=dev)
+        seeds = seeds.detach().float().contiguous()
+        drec = (seeds / ns).repeat_interleave(ns).contiguous()
+        dz = self.backward(drec, st.gen)
+        self.join()
+        lbar = reparam_kl_backward(st.lam, eps, dz.view(B, ns, nz), seeds * st.klw)
+        if K > 0:
+            total = f.grad.clone()
+            vbar = torch.zeros(B, 2 * nz, **f32)
+            u, scal = torch.empty(B, 2 * nz, **f32), torch.empty(3, **f32)
+            zpm, seeds2 = torch.empty(B, 2 * ns, nz, **f32), torch.empty(B * 2 * ns, **f32)
+            mask2 = None
+            if mask_out is not None:
+                m4 = mask_out.view(B, ns, T - 1, -1)
+                mask2 = torch.cat((m4, m4), dim=1).reshape(B * 2 * ns, T - 1, -1).contiguous()
+            for k in range(K - 1, -1, -1):
+                o = k * B * 2 * nz
+                lib.lv_savae_adjoint_f32(P(lbar), P(vbar), P(st.g_rec, o), P(st.lam_rec, o), P(eps), lr, mom, clip, float(fd_eps),
+                                         P(u), P(scal), P(zpm), P(seeds2), B, ns, nz, s)
+                self.forward(x, zpm, mask_in, mask2, p_in, p_out, want_rec=False)
+                dzp, parts = self.backward(seeds2, partial_dz=True)
+                self.join()
+                lib.lv_add_f32(P(total), P(f.grad), P(total), f.grad.numel(), s)
+                lib.lv_savae_hvp_f32(P(dzp), parts, P(eps), P(st.lam_rec, o), P(u), P(scal), P(st.klw), P(lbar), B, ns, nz, s)
+            f.grad.copy_(total)
+        return lbar
+
+    def savae_step(self, x, mulv, eps, mask_in, mask_out, p_in, p_out, seeds, steps, lr, momentum, clip, fd_eps, kl_weight):
+        """One semi-amortized step's decoder side: savae_forward, then savae_backward with `seeds` [B].  -> (the step's record, the
+        gradient with respect to lambda_0); the decoder's gradient is in flat.grad.  A timed-out persistent launch raises."""
+        st = self.savae_forward(x, mulv, eps, mask_in, mask_out, p_in, p_out, steps, lr, momentum, clip, kl_weight)
+        dmulv = self.savae_backward(st, seeds, fd_eps)
+        check_persistent_status(self)
+        return st, dmulv
 
     # ---- Hamiltonian chains (VAE.nll_ais / sample_from_posterior with transition="hmc", DESIGN.md 3.1.3) --------------------------
     def hmc_ais(self, x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep=None, iters_per_launch=None):

@@ -38,6 +38,122 @@ class _IWBoundFn(torch.autograd.Function):
         return rowscale, _eng.reparam_iw_backward(mulv, eps, wz), None, None, None, None
 
 
+class _SAVAEFn(torch.autograd.Function):
+    """(lambda_0 = mulv, decoder parameters) -> (loss [B], rec [B], kl [B]) at the refined lambda_K of VAE.loss_savae.  `route` is
+    the decoder engine (fused: engine.LSTMDecoderEngine.savae_forward / savae_backward) or a _SAVAEGeneric; the backward returns
+    the gradient with respect to lambda_0 -- the encoder's backward continues from it -- and the decoder's parameters."""
+
+    @staticmethod
+    def forward(ctx, route, cfg, x, mulv, eps, mask_in, mask_out, *params):
+        p_in, p_out, steps, lr, momentum, clip, fd_eps, kl_weight = cfg
+        st = route.savae_forward(x, mulv, eps, mask_in, mask_out, p_in, p_out, steps, lr, momentum, clip, kl_weight)
+        ctx.route, ctx.st, ctx.fd_eps = route, st, fd_eps
+        loss = st.rec + kl_weight * st.kl
+        rec, kl = st.rec.clone(), st.kl.clone()
+        ctx.mark_non_differentiable(rec, kl)
+        return loss, rec, kl
+
+    @staticmethod
+    def backward(ctx, dloss, drec, dkl):
+        route = ctx.route
+        if isinstance(route, _eng.LSTMDecoderEngine):
+            route.flat.before_autograd_backward()
+            dmulv = route.savae_backward(ctx.st, dloss, ctx.fd_eps)
+            _eng.check_persistent_status(route)
+            grads = route.flat.deliver_grads()
+        else:
+            dmulv, grads = route.savae_backward(ctx.st, dloss, ctx.fd_eps)
+        return (None, None, None, dmulv, None, None, None) + tuple(grads)
+
+
+class _SAVAEGeneric(object):
+    """Route "generic" of VAE.loss_savae: csrc/lv_savae.hip's definition over decoder.reconstruct_error and torch.autograd.grad,
+    with the same three small kernels for the per-sentence arithmetic (as VAE._svi_generic does for the refinement)."""
+
+    def __init__(self, vae):
+        self.vae = vae
+
+    def _pass(self, x, z, masks, seeds, params):
+        """reconstruct_error at z under the step's masks, differentiated with the row seeds -> (rec_s, dz, parameter gradients)."""
+        with torch.enable_grad():
+            z = z.detach().requires_grad_(True)
+            rec_s = self.vae.decoder.reconstruct_error(x, z, masks=masks)
+            g = torch.autograd.grad(rec_s, [z] + params, seeds.view_as(rec_s))
+        return rec_s.detach(), g[0].contiguous(), list(g[1:])
+
+    def savae_forward(self, x, mulv, eps, mask_in, mask_out, p_in, p_out, steps, lr, momentum, clip, kl_weight):
+        dev = x.device
+        lib, s = _eng.backend_for(dev), _eng.stream_ptr(dev)
+        P = _eng.P
+        B, ns, nz = eps.shape
+        f32 = dict(dtype=torch.float32, device=dev)
+        st = _eng._NS()
+        lam = mulv.detach().float().contiguous().clone()
+        st.g_rec, st.lam_rec = torch.empty(steps, B, 2 * nz, **f32), torch.empty(steps, B, 2 * nz, **f32)
+        st.klw = torch.full((1,), float(kl_weight), **f32)
+        st.masks = (mask_in, mask_out)
+        vel = torch.zeros(B, 2 * nz, **f32)
+        z_next, kl_next = torch.empty(B, ns, nz, **f32), torch.empty(B, **f32)
+        row = torch.full((B, ns), 1.0 / ns, **f32)
+        st.rec0 = st.kl0 = None
+        with self.vae._decoder_gradients_preserved(dev):
+            for k in range(steps):
+                z, kl = _eng.reparam_kl_forward(lam, eps)
+                rec_s, dz, _ = self._pass(x, z, st.masks, row, [])
+                if k == 0:
+                    st.rec0, st.kl0 = rec_s.sum(dim=1) / ns, kl
+                lib.lv_svi_rec_step_f32(P(dz), 1, P(eps), P(st.klw), float(lr), float(momentum), float(clip), P(lam), P(vel),
+                                        P(st.g_rec, k * B * 2 * nz), P(st.lam_rec, k * B * 2 * nz), P(z_next), P(kl_next), B, ns, nz, s)
+            st.z, st.kl = _eng.reparam_kl_forward(lam, eps)
+            with torch.no_grad():
+                st.rec = self.vae.decoder.reconstruct_error(x, st.z, masks=st.masks).sum(dim=1) / ns
+        if steps == 0:
+            st.rec0, st.kl0 = st.rec, st.kl
+        st.x, st.eps, st.lam, st.steps, st.ns = x, eps, lam, steps, ns
+        st.hyper = (float(lr), float(momentum), float(clip))
+        return st
+
+    def savae_backward(self, st, seeds, fd_eps):
+        vae = self.vae
+        x, eps, ns, K = st.x, st.eps, st.ns, st.steps
+        dev = x.device
+        lib, s = _eng.backend_for(dev), _eng.stream_ptr(dev)
+        P = _eng.P
+        B, _, nz = eps.shape
+        lr, mom, clip = st.hyper
+        mask_in, mask_out = st.masks
+        f32 = dict(dtype=torch.float32, device=dev)
+        every = list(vae.decoder._params())
+        params = [p for p in every if p.requires_grad]
+        seeds = seeds.detach().float().contiguous()
+        flat = getattr(getattr(vae.decoder, "_hip", None), "flat", None)
+        if flat is not None:
+            flat.before_autograd_backward()
+        with vae._decoder_gradients_preserved(dev):
+            _, dz, total = self._pass(x, st.z, st.masks, (seeds / ns).view(B, 1).expand(B, ns).contiguous(), params)
+            total = [g.clone() for g in total]
+            lbar = _eng.reparam_kl_backward(st.lam, eps, dz.view(B, ns, nz), seeds * st.klw)
+            if K > 0:
+                vbar = torch.zeros(B, 2 * nz, **f32)
+                u, scal = torch.empty(B, 2 * nz, **f32), torch.empty(3, **f32)
+                zpm, seeds2 = torch.empty(B, 2 * ns, nz, **f32), torch.empty(B * 2 * ns, **f32)
+                mask2 = None
+                if mask_out is not None:
+                    m4 = mask_out.view(B, ns, mask_out.shape[1], -1)
+                    mask2 = torch.cat((m4, m4), dim=1).reshape(B * 2 * ns, mask_out.shape[1], -1).contiguous()
+            for k in range(K - 1, -1, -1):
+                o = k * B * 2 * nz
+                lib.lv_savae_adjoint_f32(P(lbar), P(vbar), P(st.g_rec, o), P(st.lam_rec, o), P(eps), lr, mom, clip, float(fd_eps),
+                                         P(u), P(scal), P(zpm), P(seeds2), B, ns, nz, s)
+                _, dz2, gs = self._pass(x, zpm, (mask_in, mask2), seeds2, params)
+                for t, g in zip(total, gs):
+                    g = g.contiguous()
+                    lib.lv_add_f32(P(t), P(g), P(t), t.numel(), s)
+                lib.lv_savae_hvp_f32(P(dz2), 1, P(eps), P(st.lam_rec, o), P(u), P(scal), P(st.klw), P(lbar), B, ns, nz, s)
+        it = iter(total)
+        return lbar, tuple(next(it) if p.requires_grad else None for p in every)
+
+
 class VAE(nn.Module):
     """Encoder q(z|x), decoder p(x|z), prior N(0, I)."""
 
@@ -145,6 +261,85 @@ class VAE(nn.Module):
         klw = torch.full((1,), float(kl_weight), dtype=torch.float32, device=mulv.device)
         loss, rec = _IWBoundFn.apply(rec_s, mulv, eps, z.detach(), kl.detach(), klw)
         return loss, rec, kl.detach()
+
+    # True: loss_savae takes the decoder engine's semi-amortized step where _fused_savae_ok allows it; False forces the generic
+    # route (A/B runs, the tests' second oracle, the bench baseline)
+    fused_savae = True
+
+    def _fused_savae_ok(self, x, B, ns):
+        eng = self.decoder._hip
+        return bool(self.fused_savae and eng.savae_supported(B, ns))
+
+    def _savae_arguments(self, who, x, svi_steps, svi_lr, svi_momentum, svi_clip, fd_eps, nsamples):
+        """The refusals of semi-amortized training, all of them before anything is launched."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("%s: variable-length batches (x, lengths) are not supported; batch by length" % who)
+        eng = getattr(self.decoder, "_hip", None)
+        if not isinstance(eng, _eng.LSTMDecoderEngine) or type(self.decoder).__name__ != "LSTMDecoder":
+            raise ValueError("%s: an LSTMDecoder is expected, got %s" % (who, type(self.decoder).__name__))
+        for e in (eng, getattr(self.encoder, "_hip", None)):
+            if getattr(e, "precision", "f32") != "f32":
+                raise ValueError("%s: precision 'f32' only -- the Hessian-vector products are differences of gradients divided by the "
+                                 "step, and bf16's gradient rounding (2^-9) divided by fd_eps would swamp them" % who)
+        if not (torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.int64):
+            raise ValueError("%s: x is an int64 tensor (batch, seq_len)" % who)
+        if int(svi_steps) < 0 or int(nsamples) < 1:
+            raise ValueError("%s: svi_steps >= 0 and nsamples >= 1 expected" % who)
+        if not (float(svi_lr) > 0.0 and float(svi_clip) > 0.0 and float(fd_eps) > 0.0 and 0.0 <= float(svi_momentum) < 1.0):
+            raise ValueError("%s: svi_lr > 0, svi_clip > 0, fd_eps > 0 and 0 <= svi_momentum < 1 expected" % who)
+
+    def _savae_noise(self, who, x, nsamples, noise):
+        """noise = (eps, mask_in, mask_out) checked against the step's shapes -> the three tensors (masks uint8 or None)."""
+        B, T = x.shape
+        dev = x.device
+        dec = self.decoder
+        if not (isinstance(noise, (tuple, list)) and len(noise) == 3):
+            raise ValueError("%s: noise is (eps, mask_in, mask_out)" % who)
+        eps, m_in, m_out = noise
+        if not torch.is_tensor(eps) or tuple(eps.shape) != (B, nsamples, self.nz) or eps.dtype != torch.float32 or eps.device != dev:
+            raise ValueError("%s: eps must be a float32 tensor of shape (%d, %d, %d) on %s" % (who, B, nsamples, self.nz, dev))
+        for name, m, shape in (("mask_in", m_in, (B, T - 1, dec.ni)), ("mask_out", m_out, (B * nsamples, T - 1, dec.nh))):
+            if m is not None and not (torch.is_tensor(m) and tuple(m.shape) == shape and m.device == dev
+                                      and m.dtype in (torch.uint8, torch.bool, torch.float32)):
+                raise ValueError("%s: %s must be a keep-mask of shape %s (uint8, bool or float32) on %s" % (who, name, shape, dev))
+        cast = lambda m: None if m is None else m.to(torch.uint8).contiguous()
+        return eps.contiguous(), cast(m_in), cast(m_out)
+
+    def loss_savae(self, x, kl_weight=1.0, svi_steps=20, svi_lr=1.0, svi_momentum=0.5, svi_clip=5.0, fd_eps=1e-2, nsamples=1,
+                   noise=None):
+        """Semi-amortized training (SA-VAE, Kim et al. 2018) -> (loss, rec, KL), each (batch,), at the posterior
+        lambda_K that `svi_steps` steps of refine_posterior's update reach from the encoder's output lambda_0 -- under THIS step's
+        noise and dropout masks, the same in every decoder pass of the step.  rec and KL are detached.  `loss.mean().backward()` (or
+        any seeds) differentiates THROUGH the refinement: the decoder's parameters get d loss / d theta at lambda_K plus the
+        refinement's dependence on theta, the encoder is reached through lambda_0 only.  The Hessian-vector products of that backward
+        pass are central differences of gradients at lambda_k +- e u with e = fd_eps * max(1, max|lambda_k|) (csrc/lv_savae.hip).
+        A step costs K forwards and K backwards to z for the refinement, one full forward and backward at lambda_K, and K full passes
+        on twice the rows.  svi_steps = 0 is the ordinary ELBO.
+
+        noise = (eps, mask_in, mask_out): eps (batch, nsamples, nz) float32; keep-masks (batch, T-1, ni) and (batch * nsamples, T-1,
+        dec_nh) or None; otherwise drawn where `loss` draws them.  Exact f32 only, LSTM decoder, equal-length batches.
+        Routes (class switch fused_savae = False forces the second): "fused", engine.LSTMDecoderEngine.savae_forward /
+        savae_backward; "generic", the same definition over decoder.reconstruct_error and torch.autograd.grad."""
+        who = "loss_savae"
+        self._savae_arguments(who, x, svi_steps, svi_lr, svi_momentum, svi_clip, fd_eps, nsamples)
+        nsamples, svi_steps = int(nsamples), int(svi_steps)
+        if noise is not None:
+            noise = self._savae_noise(who, x, nsamples, noise)
+        B, T = x.shape
+        dec = self.decoder
+        mulv = self.encoder._forward_mulv(x)
+        if noise is None:
+            eps = self.encoder._draw_eps(B, nsamples, self.nz, x.device)
+            m_in, m_out = dec._draw_masks(B, T - 1, x.device)
+            if nsamples > 1 and m_out is not None:
+                m_out = torch.empty(B * nsamples, T - 1, dec.nh, device=x.device).bernoulli_(1 - dec.dropout_out.p).to(torch.uint8)
+        else:
+            eps, m_in, m_out = noise
+        dec._hip.ensure(x.device)
+        route = dec._hip if self._fused_savae_ok(x, B, nsamples) else _SAVAEGeneric(self)
+        cfg = (dec.dropout_in.p, dec.dropout_out.p, svi_steps, float(svi_lr), float(svi_momentum), float(svi_clip), float(fd_eps),
+               float(kl_weight))
+        return _SAVAEFn.apply(route, cfg, x, mulv, eps, m_in, m_out, *dec._params())
 
     def KL(self, x):
         return self.encode(x, 1)[1]

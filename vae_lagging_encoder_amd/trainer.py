@@ -877,6 +877,90 @@ class AggressiveTextTrainer(object):
         return steps
 
 
+class SemiAmortizedTextTrainer(AggressiveTextTrainer):
+    """Fused driver for semi-amortized training (SA-VAE, Kim et al. 2018): AggressiveTextTrainer's step -- same
+    surface, clip over both sides, transaction gate and optimizers -- whose forward and backward are the semi-amortized ones:
+    the ELBO at the posterior `svi_steps` refinement steps reach from the encoder's output, differentiated through the refinement
+    (engine.LSTMDecoderEngine.savae_step, csrc/lv_savae.hip).  read_stats() reports loss_sum / rec_sum / kl_sum at the refined
+    posterior and loss0_sum = sum_b L_b(lambda_0), the same objective at the encoder's output: their difference is the
+    amortization gap the refinement closed.  svi_steps = 0 is the ordinary step.  Single GPU, eager mode, one micro-batch,
+    decoder_grads = "full", fold_norm off, precision "f32"."""
+
+    def __init__(self, vae, svi_steps=20, svi_lr=1.0, svi_momentum=0.5, svi_clip=5.0, fd_eps=1e-2, **kw):
+        fenced = [n for n, on in (("grad_sync", kw.get("grad_sync") is not None), ("use_graph=True", bool(kw.get("use_graph", False))),
+                                  ("micro_batches > 1", int(kw.get("micro_batches", 1)) > 1),
+                                  ("decoder_grads='norm'", kw.get("decoder_grads", "full") != "full"),
+                                  ("fold_norm=True", bool(kw.get("fold_norm", False))),
+                                  ("objective='iw'", kw.get("objective", "elbo") != "elbo")) if on]
+        if fenced:
+            raise ValueError("semi-amortized training runs on a single GPU in eager mode with micro_batches = 1, decoder_grads = "
+                             "'full' and fold_norm off; not implemented together with: %s" % ", ".join(fenced))
+        if kw.get("precision", "f32") != "f32":
+            raise ValueError("semi-amortized training: precision 'f32' only -- the Hessian-vector products are differences of "
+                             "gradients divided by the step, and bf16's gradient rounding divided by fd_eps would swamp them")
+        if type(vae.decoder).__name__ != "LSTMDecoder":
+            raise ValueError("semi-amortized training: an LSTMDecoder is expected, got %s" % type(vae.decoder).__name__)
+        if int(svi_steps) < 0:
+            raise ValueError("svi_steps must be >= 0, not %r" % (svi_steps,))
+        if not (float(svi_lr) > 0.0 and float(svi_clip) > 0.0 and float(fd_eps) > 0.0 and 0.0 <= float(svi_momentum) < 1.0):
+            raise ValueError("svi_lr > 0, svi_clip > 0, fd_eps > 0 and 0 <= svi_momentum < 1 expected")
+        kw["fold_norm"] = False
+        super(SemiAmortizedTextTrainer, self).__init__(vae, **kw)
+        self.svi = (int(svi_steps), float(svi_lr), float(svi_momentum), float(svi_clip), float(fd_eps))
+        # [0] loss0_sum over committed steps, [1] that of the step in flight (committed behind the transaction gate)
+        self.scal0 = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def read_stats(self):
+        out = super(SemiAmortizedTextTrainer, self).read_stats()          # (settles the transaction block first)
+        out["loss0_sum"] = float(self.scal0[0])
+        return out
+
+    def reset_stats(self):
+        super(SemiAmortizedTextTrainer, self).reset_stats()
+        self.scal0[0] = 0
+
+    def step(self, x, kl_weight, noise=None, update="both"):
+        if noise is not None:
+            self._check_noise(x, noise)
+        super(SemiAmortizedTextTrainer, self).step(x, kl_weight, noise=noise, update=update)
+
+    def _fwd_bwd_armed(self, st, draw):
+        lib, s = self.lib, _eng.stream_ptr(self.device)
+        B, T = st.x.shape
+        dec = self.vae.decoder
+        train = self.vae.training
+        use_in = train and dec.dropout_in.p > 0
+        use_out = train and dec.dropout_out.p > 0
+        if draw:
+            lib.lv_rng_noise_step(P(st.eps), st.eps.numel(), P(st.m_in) if use_in else None, st.m_in.numel(),
+                                  1.0 - dec.dropout_in.p, P(st.m_out) if use_out else None, st.m_out.numel(),
+                                  1.0 - dec.dropout_out.p, P(self.rng_state), 1, s)
+        m_in = st.m_in if use_in else None
+        m_out = st.m_out if use_out else None
+        if not self.dec.savae_supported(B, self.nsamples):
+            raise _eng._lib.LvaeError("semi-amortized step: %d sentences x %d samples is beyond the decoder's one-launch ends "
+                                      "(VAE.loss_savae's generic route takes such batches)" % (B, self.nsamples))
+        K, lr, mom, clip, fd_eps = self.svi
+        mulv = self.enc.forward(st.xin, x_key=st.x_key)
+        r = self.dec.savae_forward(st.xin, mulv, st.eps, m_in, m_out, dec.dropout_in.p, dec.dropout_out.p, K, lr, mom, clip,
+                                   self._klw_host)
+        # the report sums of the step in flight: committed by the transaction gate (scal[10..12]) and by _clip_and_step (scal0)
+        st.loss = r.rec + self._klw_host * r.kl
+        for i, t in enumerate((st.loss, r.rec, r.kl)):
+            lib.lv_sum_accum_f32(P(t), B, self._s(10 + i), s)
+        st.loss0 = r.rec0 + self._klw_host * r.kl0
+        self.scal0[1] = 0
+        lib.lv_sum_accum_f32(P(st.loss0), B, P(self.scal0, 1), s)
+        dmulv = self.dec.savae_backward(r, st.gl, fd_eps)
+        self.enc.backward(dmulv)
+        self.dec.join()
+
+    def _clip_and_step(self, update, dec_ss=None, embed_rows=None):
+        super(SemiAmortizedTextTrainer, self)._clip_and_step(update, dec_ss, embed_rows=embed_rows)
+        # the gate has decided: a voided step (scal[8] up) adds nothing
+        self.scal0[0] += torch.where(self.scal[8] == 0, self.scal0[1], torch.zeros_like(self.scal0[1]))
+
+
 class AggressiveImageTrainer(object):
     """Fused driver for the Omniglot aggressive loop (reference image.py:295-348): one `step()` = zero_grad, VAE.loss,
     loss.mean().backward(), clip_grad_norm_(all params, 5.0), Adam step on the encoder (image.py:302-314), as a

@@ -19,7 +19,7 @@ import torch
 
 from . import engine as _eng
 from . import evaluation as E
-from .trainer import AggressiveImageTrainer, AggressiveTextTrainer
+from .trainer import AggressiveImageTrainer, AggressiveTextTrainer, SemiAmortizedTextTrainer
 
 CLIP_GRAD = 5.0          # text.py:17-20
 DECAY_EPOCH = 2
@@ -65,7 +65,8 @@ def _objective(args, trainer):
 class TextTrainingLoop(object):
     """args fields read (text.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
     iw_nsamples, momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...)), and
-    objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...))."""
+    objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...)), and svi_steps (missing or 0: the ordinary steps;
+    K > 0: semi-amortized training, SemiAmortizedTextTrainer, with svi_lr, svi_momentum, svi_clip and fd_eps)."""
 
     def __init__(self, vae, train_batches, val_batches, test_batches, args, n_train_sentences=None, trainer=None,
                  log=print, np_rng=None, seed=783435, noise_fn=None, epoch_hook=None):
@@ -86,6 +87,19 @@ class TextTrainingLoop(object):
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
         self.objective = _objective(args, trainer)
+        # args.svi_steps = K > 0: semi-amortized training (SemiAmortizedTextTrainer) with args.svi_lr, svi_momentum,
+        # svi_clip and fd_eps (Kim et al.'s defaults when missing); missing or 0: the ordinary steps
+        self.svi_steps = int(getattr(args, "svi_steps", 0) or 0)
+        if self.svi_steps < 0:
+            raise ValueError("args.svi_steps must be >= 0, not %r" % (self.svi_steps,))
+        if self.svi_steps > 0 and (bool(args.aggressive) or self.objective == "iw"):
+            raise ValueError("args.svi_steps = %d (semi-amortized training) runs neither with aggressive = 1 nor with objective = 'iw'"
+                             % self.svi_steps)
+        if self.svi_steps > 0 and trainer is None:
+            trainer = SemiAmortizedTextTrainer(vae, svi_steps=self.svi_steps, svi_lr=float(getattr(args, "svi_lr", 1.0)),
+                                               svi_momentum=float(getattr(args, "svi_momentum", 0.5)),
+                                               svi_clip=float(getattr(args, "svi_clip", 5.0)), fd_eps=float(getattr(args, "fd_eps", 1e-2)),
+                                               lr=1.0, clip=CLIP_GRAD, seed=seed, nsamples=self.nsamples, momentum=self.momentum)
         self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
                                                                                  nsamples=self.nsamples, momentum=self.momentum,
                                                                                  objective=self.objective)
