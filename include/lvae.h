@@ -381,6 +381,37 @@ int lv_loss_assemble_iw_rng_f32(const float* nll, const float* mulv, const float
  * dmu_j = sum_s c_s z_sj, dlogvar_j = sum_s c_s z_sj eps_sj sigma_j / 2 - sum_s c_s / 2, c = wz [B][ns] */
 int lv_reparam_iw_bwd_f32(const float* mulv, const float* eps, const float* wz, float* dmulv, int B, int ns, int nz, void* stream);
 
+/* ---- the free-bits (KL thresholding) objective (lv_freebits.hip; Kingma et al. 2016, Chen et al. 2017, Li et al. 2019) ----
+ * Per sentence b and latent dimension j, KL_bj = 0.5 (mu_bj^2 + exp(lv_bj) - lv_bj - 1).  lam = free_bits >= 0, in nats PER LATENT
+ * DIMENSION in every mode.  The gate g is a constant of the step (no gradient flows through it); all comparisons are strict (>).
+ *   mode 0 "dim":        statistic KL_bj;                                       g_bj = KL_bj > lam;    kl_obj_b = sum_j (g_bj ? KL_bj : lam)
+ *   mode 1 "batch_dim":  m_j = (sum_b KL_bj) / B, summed in ascending b;        g_bj = g_j = m_j > lam; kl_obj_b = sum_j (g_j ? KL_bj : lam)
+ *   mode 2 "batch":      m = (sum_b kl_b) / B, ascending b, kl_b = sum_j KL_bj; g_bj = g = m > tau;    kl_obj_b = g ? kl_b : tau,
+ *                        tau = (float)(nz * lam) formed on the host in double
+ * loss_b = rec_b + w * kl_obj_b ("batch_dim": mean_b loss_b = mean_b rec_b + w sum_j max(lam, m_j)).  Gradient of the KL term:
+ * d kl_obj_b / d mu_bj = g_bj mu_bj, d kl_obj_b / d lv_bj = g_bj 0.5 (exp(lv_bj) - 1); the path through z is unchanged.  The
+ * REPORTED KL (VAE.loss's third value, the trainers' kl_sum) stays the analytic, unthresholded one; loss_sum is the objective that
+ * was minimised; no evaluation function applies free bits.
+ *
+ * mulv [B][2nz] -> kl_obj [B], gate [B][nz] (0.0f / 1.0f), stat (may be NULL; [B][nz] / [nz] / [1] in mode 0 / 1 / 2: the
+ * statistic that was compared).  One workgroup, no atomics, batch sums in ascending b; any B >= 1, nz >= 1.  A mode outside 0..2
+ * or a NULL output returns before any write.  This raw entry takes any lam (a negative one opens every gate; the public layers
+ * refuse it).  With every gate open kl_obj is lv_reparam_kl_fwd_f32's kl bit for bit. */
+int lv_kl_freebits_fwd_f32(const float* mulv, float lam, int mode, float* kl_obj, float* gate, float* stat, int B, int nz,
+                           void* stream);
+/* lv_reparam_kl_bwd_f32 with dkl[b] * gate[b][j] in place of dkl[b]; a gate of all ones gives its bits */
+int lv_reparam_kl_gated_bwd_f32(const float* mulv, const float* eps, const float* dz, const float* dkl, const float* gate,
+                                float* dmulv, int B, int ns, int nz, void* stream);
+/* lv_loss_assemble_ns_f32 with loss[b] = rec[b] + w*kl_obj[b]; acc_dev[2] += sum_b kl[b] stays the analytic KL.  kl_obj = kl
+ * gives lv_loss_assemble_ns_f32's bits. */
+int lv_loss_assemble_fb_f32(const float* nll, const float* kl, const float* kl_obj, const float* kl_weight_dev, const float* g_loss,
+                            float* loss, float* rec, float* rowscale, float* dkl, float* acc_dev, int T, int B, int ns,
+                            void* stream);
+/* the same + rng_state[1] += rng_inc, as lv_loss_assemble_ns_rng_f32 */
+int lv_loss_assemble_fb_rng_f32(const float* nll, const float* kl, const float* kl_obj, const float* kl_weight_dev,
+                                const float* g_loss, float* loss, float* rec, float* rowscale, float* dkl, float* acc_dev, int T,
+                                int B, int ns, uint64_t* rng_state, uint64_t rng_inc, void* stream);
+
 /* ---- the batch-sized ends of the two LSTM networks, one launch each (lv_head.hip) --------------------------------------
  * LSTMEncoder's head + GaussianEncoderBase.encode (enc_lstm.py:62-64, encoder.py:40-57): mulv = hT . W_lin^T,
  * z = mu + eps*exp(logvar/2), kl = 0.5*sum(mu^2 + exp(logvar) - logvar - 1).  hT [B][H], W_lin [2nz][H], eps/z [B][ns][nz] */
@@ -397,6 +428,11 @@ int lv_enc_head_bwd_f32(const float* mulv, const float* eps, const float* dz, in
 int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz,
                            const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin, int B, int H, int ns,
                            int nz, void* stream);
+/* lv_enc_head_bwd_f32 under free bits: dkl[b] * gate[b][j] (gate [B][nz] of lv_kl_freebits_fwd_f32) in place of dkl[b].  With a
+ * gate of all ones every output is bit-identical to lv_enc_head_bwd_f32's. */
+int lv_enc_head_gated_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* dkl,
+                              const float* gate, const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin,
+                              int B, int H, int ns, int nz, void* stream);
 /* LSTMDecoder.decode's z-dependent prologue (dec_lstm.py:95-101): c0 = z W_trans^T, h0 = tanh(c0) (G7) and
  * Zp = z W_ih[:, col0:col0+nz]^T + b_ih + b_hh, the contribution of cat((word_embed, z_), -1) to the input projection;
  * Zp gate-major [B][4H], or with column 4u+g (unit_major != 0) for the unit-major Gx epilogue */

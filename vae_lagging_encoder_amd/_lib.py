@@ -62,6 +62,11 @@ SIGNATURES = {
     "lv_loss_assemble_iw_rng_f32": [_vp] * 13 + [_i, _i, _i, _i, _vp, _u64, _vp],
     "lv_reparam_iw_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_enc_head_iw_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lv_kl_freebits_fwd_f32": [_vp, _f, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "lv_reparam_kl_gated_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_loss_assemble_fb_f32": [_vp] * 10 + [_i, _i, _i, _vp],
+    "lv_loss_assemble_fb_rng_f32": [_vp] * 10 + [_i, _i, _i, _vp, _u64, _vp],
+    "lv_enc_head_gated_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_enc_head_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_enc_head_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_dec_tail_parts": [_i],

@@ -96,6 +96,8 @@ __global__ __launch_bounds__(256) void enc_head_fwd_kernel(const float* __restri
     }
 }
 
+__device__ __forceinline__ const float* head_gate(const float* g) { return g; }
+
 // ---- encoder head backward: dmulv from (dz, dKL); dh_T = dmulv . W_lin ; dW_lin = dmulv^T . h_T --------------------------
 // grid ceil(H/64): a workgroup covers 64 columns h.  Everything it needs -- dmulv [B][2nz], the W_lin columns [2nz][64]
 // and the h_T columns [B][64] -- is staged in LDS with fully parallel loads first; the dot products then run out of LDS
@@ -104,12 +106,15 @@ __global__ __launch_bounds__(256) void enc_head_fwd_kernel(const float* __restri
 // IW (objective "iw", lv_iw.hip): `dkl` is wz [B][ns], c_s = beta * g * wn_s, and the analytic-KL terms give way to the per-sample
 // ones: t_sj = dz_sj + c_s z_sj, dmu_j = sum_s t_sj, dlogvar_j = sum_s t_sj 1/2 eps_sj sigma_j - 1/2 sum_s c_s.  With wz all zeros
 // every operation reduces to the one the plain kernel does with dkl all zeros: the same bits.
-template <int HB_COLS, bool IW>
+// GATED (free bits, lv_freebits.hip): the analytic-KL seed of dimension j is dkl_b * gate_bj, gate [B][nz] of 0.0f / 1.0f;
+// with a gate of all ones the product is dkl_b itself: the same bits.
+// The gate travels as a trailing parameter pack (empty, or one `const float*`): the ungated kernels keep their argument list.
+template <int HB_COLS, bool IW, class... Gate>
 __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restrict__ mulv, const float* __restrict__ eps,
                                                            const float* __restrict__ dz, int parts, const float* __restrict__ dkl,
                                                            const float* __restrict__ hT, const float* __restrict__ wlin,
                                                            float* __restrict__ dmulv, float* __restrict__ dhT,
-                                                           float* __restrict__ gwlin, int B, int H, int ns, int nz) {
+                                                           float* __restrict__ gwlin, int B, int H, int ns, int nz, Gate... gate) {
     LV_DYN_SHARED(smem);
     const int nz2 = 2 * nz;
     float* sd = reinterpret_cast<float*>(smem);           // [B][2nz]   dmulv
@@ -194,7 +199,8 @@ __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restri
                 gz += g;
                 gze += g * eps[zi];
             }
-            const float gk = dkl[bb];
+            float gk = dkl[bb];
+            if constexpr (sizeof...(Gate) > 0) gk = gk * head_gate(gate...)[(long)bb * nz + j];
             dm = gz + gk * m;
             dl = gze * (0.5f * sdv) + gk * (0.5f * (expf(lv) - 1.f));
         }
@@ -369,6 +375,23 @@ extern "C" int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const
     if ((base + per_col * 16) * sizeof(float) <= 64000)
         LV_LAUNCH((enc_head_bwd_kernel<16, true>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
                   mulv, eps, dz, dz_parts, wz, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz);
+    else
+        return LV_ERR_UNSUPPORTED;
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// lv_enc_head_bwd_f32 under free bits (lv_freebits.hip): gate [B][nz] from lv_kl_freebits_fwd_f32 multiplies the analytic-KL seed
+// per dimension (dkl_b * gate_bj in place of dkl_b).  With a gate of all ones every output is bit-identical to the plain entry's.
+extern "C" int lv_enc_head_gated_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* dkl,
+                                         const float* gate, const float* hT, const float* wlin, float* dmulv, float* dhT,
+                                         float* gwlin, int B, int H, int ns, int nz, void* stream) {
+    if (!mulv || !eps || !dz || !dkl || !gate || !hT || !wlin || !dmulv || !dhT || !gwlin) return LV_ERR_ARG;
+    if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
+    const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
+    if ((base + per_col * 16) * sizeof(float) <= 64000)
+        LV_LAUNCH((enc_head_bwd_kernel<16, false, const float*>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256),
+                  (base + per_col * 16) * sizeof(float), stream, mulv, eps, dz, dz_parts, dkl, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz, gate);
     else
         return LV_ERR_UNSUPPORTED;
     LV_CHECK_LAUNCH();

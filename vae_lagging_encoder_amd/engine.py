@@ -1304,7 +1304,9 @@ class LSTMEncoderEngine(object):
         head = (eps, dz [parts][B][ns][nz], parts, dkl [B]) instead of dmulv: the backward of reparameterise + KL runs in
         the head's launch (fused driver; dmulv is then produced into the workspace).  A fifth element "iw" selects the
         importance-weighted objective's head backward (lv_enc_head_iw_bwd_f32): the fourth is then wz [B][ns], the per-sample
-        seeds of lv_loss_assemble_iw_f32, in place of the analytic-KL seed."""
+        seeds of lv_loss_assemble_iw_f32, in place of the analytic-KL seed.  A fifth element that is a tensor is the free-bits gate
+        [B][nz] of lv_kl_freebits_fwd_f32: the analytic-KL seed of dimension j is then dkl[b] * gate[b][j] (lv_enc_head_gated_bwd_f32,
+        or lv_reparam_kl_gated_bwd_f32 in front of the GEMM sequence beyond fused_ends_ok)."""
         x, B, T, g = self.last
         if gen is not None and gen != g:
             raise _lib.LvaeError("encoder activations were overwritten by a later forward(); the HIP engine keeps "
@@ -1315,23 +1317,33 @@ class LSTMEncoderEngine(object):
         V, ni, H, nz2 = self.dims()
         w = self._ws(B, T)
         v, gv = f.views, f.gviews
-        iw = head is not None and len(head) == 5 and head[4] == "iw"
+        gate = head[4] if head is not None and len(head) == 5 and torch.is_tensor(head[4]) else None
+        iw = head is not None and len(head) == 5 and gate is None and head[4] == "iw"
         if head is not None:
             head = head[:4]
+        if gate is not None and not (gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (B, nz2 // 2)):
+            raise _lib.LvaeError("free-bits gate: a contiguous float32 [%d][%d] tensor expected" % (B, nz2 // 2))
         if iw and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
             raise _lib.LvaeError("objective 'iw' runs on the one-launch encoder head (lv_enc_head_iw_bwd_f32); B = %d, nsamples = %d, "
                                  "nz = %d is beyond its LDS budget" % (B, head[0].shape[1], nz2 // 2))
         if head is not None and not fused_ends_ok(B, nz2 // 2, head[0].shape[1]):
             eps, dz, parts, dkl = head
             assert parts == 1
-            lib.lv_reparam_kl_bwd_f32(P(w.mulv), P(eps), P(dz), P(dkl), P(w.dmulv), B, eps.shape[1], nz2 // 2, s)
+            if gate is not None:
+                lib.lv_reparam_kl_gated_bwd_f32(P(w.mulv), P(eps), P(dz), P(dkl), P(gate), P(w.dmulv), B, eps.shape[1], nz2 // 2, s)
+            else:
+                lib.lv_reparam_kl_bwd_f32(P(w.mulv), P(eps), P(dz), P(dkl), P(w.dmulv), B, eps.shape[1], nz2 // 2, s)
             _gemm(lib, s, 0, 0, B, H, nz2, P(w.dmulv), nz2, P(v["linear.weight"]), H, P(w.dhT), H)
             _gemm(lib, s, 1, 0, nz2, H, B, P(w.dmulv), nz2, P(w.hs, T * B * H), H, P(gv["linear.weight"]), H)
         elif head is not None:
             eps, dz, parts, dkl = head
-            head_bwd = lib.lv_enc_head_iw_bwd_f32 if iw else lib.lv_enc_head_bwd_f32
-            head_bwd(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(w.hs, T * B * H), P(v["linear.weight"]), P(w.dmulv),
-                     P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
+            if gate is not None:
+                lib.lv_enc_head_gated_bwd_f32(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(gate), P(w.hs, T * B * H), P(v["linear.weight"]),
+                                              P(w.dmulv), P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
+            else:
+                head_bwd = lib.lv_enc_head_iw_bwd_f32 if iw else lib.lv_enc_head_bwd_f32
+                head_bwd(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(w.hs, T * B * H), P(v["linear.weight"]), P(w.dmulv),
+                         P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
         else:
             dmulv = dmulv.contiguous()
             # head: dh_T = dmulv . W_lin ; dW_lin = dmulv^T . h_T
@@ -2340,6 +2352,51 @@ def reparam_kl_backward(mulv, eps, dz, dkl):
     # (contiguous copies are held in locals until the launch is queued: a temporary's block may be handed out again at once)
     mulv_c, eps_c, dz_c, dkl_c = mulv.contiguous(), eps.contiguous(), dz.contiguous(), dkl.contiguous()
     lib.lv_reparam_kl_bwd_f32(P(mulv_c), P(eps_c), P(dz_c), P(dkl_c), P(dmulv), B, ns, nz, s)
+    return dmulv
+
+
+FREE_BITS_MODES = {"dim": 0, "batch_dim": 1, "batch": 2}
+
+
+def check_free_bits(free_bits, mode):
+    """(lambda, mode number) of a free-bits objective (csrc/lv_freebits.hip), or ValueError -- before anything is launched."""
+    try:
+        lam = float(free_bits)
+    except (TypeError, ValueError):
+        raise ValueError("free_bits: a number of nats per latent dimension >= 0 (or None), not %r" % (free_bits,))
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("free_bits must be finite and >= 0, not %r" % (free_bits,))
+    if mode not in FREE_BITS_MODES:
+        raise ValueError("free_bits_mode: 'dim', 'batch_dim' or 'batch', not %r" % (mode,))
+    return lam, FREE_BITS_MODES[mode]
+
+
+def kl_freebits_forward(mulv, lam, mode, want_stat=False):
+    """mulv [B][2nz] -> kl_obj [B] (the thresholded KL), gate [B][nz] of 0.0 / 1.0 (and, want_stat, the statistic that was
+    compared: [B][nz] / [nz] / [1] for mode "dim" / "batch_dim" / "batch").  One launch (lv_kl_freebits_fwd_f32)."""
+    lam, mode_no = check_free_bits(lam, mode)
+    lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
+    B, nz2 = mulv.shape
+    nz = nz2 // 2
+    mulv_c = mulv.contiguous()
+    f32 = dict(dtype=torch.float32, device=mulv.device)
+    kl_obj, gate = torch.empty(B, **f32), torch.empty(B, nz, **f32)
+    stat = torch.empty(((B, nz), (nz,), (1,))[mode_no], **f32) if want_stat else None
+    lib.lv_kl_freebits_fwd_f32(P(mulv_c), lam, mode_no, P(kl_obj), P(gate), None if stat is None else P(stat), B, nz, s)
+    return (kl_obj, gate, stat) if want_stat else (kl_obj, gate)
+
+
+def reparam_kl_gated_backward(mulv, eps, dz, dkl, gate):
+    """reparam_kl_backward with dkl[b] * gate[b][j] in place of dkl[b] (lv_reparam_kl_gated_bwd_f32)."""
+    lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
+    B, nz2 = mulv.shape
+    nz = nz2 // 2
+    ns = eps.shape[1]
+    if tuple(gate.shape) != (B, nz):
+        raise ValueError("gate has shape %s; (%d, %d) expected" % (tuple(gate.shape), B, nz))
+    dmulv = torch.empty_like(mulv)
+    mulv_c, eps_c, dz_c, dkl_c, gate_c = mulv.contiguous(), eps.contiguous(), dz.contiguous(), dkl.contiguous(), gate.contiguous()
+    lib.lv_reparam_kl_gated_bwd_f32(P(mulv_c), P(eps_c), P(dz_c), P(dkl_c), P(gate_c), P(dmulv), B, ns, nz, s)
     return dmulv
 
 

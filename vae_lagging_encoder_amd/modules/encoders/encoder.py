@@ -29,6 +29,28 @@ class _ReparamKLFn(torch.autograd.Function):
         return _eng.reparam_kl_backward(mulv, eps, dz, dkl), None
 
 
+class _ReparamKLFreeBitsFn(torch.autograd.Function):
+    """_ReparamKLFn under free bits (csrc/lv_freebits.hip): -> z, kl_obj (the thresholded KL, what the loss takes), kl (the
+    analytic KL, reported only: no gradient), gate [B][nz].  The gate is a constant of the step: the backward is the gated kernel."""
+
+    @staticmethod
+    def forward(ctx, mulv, eps, lam, mode):
+        z, kl = _eng.reparam_kl_forward(mulv, eps)
+        kl_obj, gate = _eng.kl_freebits_forward(mulv, lam, mode)
+        ctx.save_for_backward(mulv, eps, gate)
+        ctx.mark_non_differentiable(kl, gate)
+        return z, kl_obj, kl, gate
+
+    @staticmethod
+    def backward(ctx, dz, dkl_obj, _dkl, _dgate):
+        mulv, eps, gate = ctx.saved_tensors
+        if dz is None:
+            dz = torch.zeros_like(eps)
+        if dkl_obj is None:
+            dkl_obj = torch.zeros(mulv.shape[0], dtype=mulv.dtype, device=mulv.device)
+        return _eng.reparam_kl_gated_backward(mulv, eps, dz, dkl_obj, gate), None, None, None
+
+
 class GaussianEncoderBase(nn.Module):
     """q(z|x) = N(mu(x), diag(exp(logvar(x))))."""
 

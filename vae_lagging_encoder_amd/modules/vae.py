@@ -231,15 +231,33 @@ class VAE(nn.Module):
         """-> mu (batch, nz), logvar (batch, nz)."""
         return self.encoder(x)
 
-    def loss(self, x, kl_weight, nsamples=1, noise=None):
+    def loss(self, x, kl_weight, nsamples=1, noise=None, free_bits=None, free_bits_mode="dim"):
         """-> (rec + kl_weight*KL, rec, KL), each (batch,).
 
         noise = (eps, mask_in, mask_out) injects the random draws of this call (parity tests); the default draws
-        them from torch's device generator at the same three places the reference does."""
+        them from torch's device generator at the same three places the reference does.
+
+        free_bits = lambda >= 0 (nats per latent dimension; None: off, the code path above unchanged) minimises the free-bits
+        objective instead (csrc/lv_freebits.hip): -> (rec + kl_weight*kl_obj, rec, KL) with kl_obj the KL
+        thresholded per free_bits_mode -- "dim" (each KL_bj against lambda), "batch_dim" (the batch mean of each dimension against
+        lambda; Kingma et al.'s form) or "batch" (the batch mean of the whole KL against nz*lambda) -- and KL the analytic,
+        unthresholded one, for reports (detached).  The gate is a constant of the step.  free_bits = 0.0 takes the gated route (a
+        dimension whose KL is exactly 0 closes its gate): not promised bit-equal to None.  The gate of the last call is kept as
+        self.last_free_bits_gate [batch][nz]."""
+        if free_bits is not None:
+            _eng.check_free_bits(free_bits, free_bits_mode)               # refusals before anything is launched
         eps, masks = (None, None) if noise is None else (noise[0], (noise[1], noise[2]))
         x = self._batch(x)
-        z, kl = self.encode(x, nsamples, eps=eps)
         dec_extra = {} if masks is None else {"masks": masks}
+        if free_bits is not None:
+            from .encoders.encoder import _ReparamKLFreeBitsFn
+            mulv = self.encoder._forward_mulv(x)
+            eps = self.encoder._draw_eps(mulv.shape[0], nsamples, mulv.shape[1] // 2, mulv.device, eps)
+            z, kl_obj, kl, gate = _ReparamKLFreeBitsFn.apply(mulv, eps, float(free_bits), free_bits_mode)
+            self.last_free_bits_gate = gate
+            rec = self.decoder.reconstruct_error(x, z, **dec_extra).mean(dim=1)
+            return rec + kl_weight * kl_obj, rec, kl
+        z, kl = self.encode(x, nsamples, eps=eps)
         rec = self.decoder.reconstruct_error(x, z, **dec_extra).mean(dim=1)
         return rec + kl_weight * kl, rec, kl
 

@@ -73,8 +73,19 @@ class AggressiveTextTrainer(object):
 
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
                  precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
-                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0, objective="elbo"):
-        """objective = "elbo" (default: rec averaged over the samples + kl_weight * analytic KL, VAE.loss) or "iw": the step minimises
+                 optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0, objective="elbo", free_bits=None,
+                 free_bits_mode="dim"):
+        """free_bits = lambda >= 0 (nats per latent dimension; None: off, every launch of the step is the one it was): the step
+        minimises the free-bits objective rec + kl_weight * kl_obj (csrc/lv_freebits.hip), kl_obj the KL thresholded
+        per free_bits_mode -- "dim" (each KL_bj against lambda), "batch_dim" (each dimension's batch mean against lambda) or "batch"
+        (the batch mean of the whole KL against nz * lambda).  lambda and the mode are fixed at construction (launch constants, also
+        of a captured hipGraph).  Three launches differ from the plain step: lv_kl_freebits_fwd_f32 behind the encoder's forward,
+        lv_loss_assemble_fb[_rng]_f32 in place of the loss assembly, and the gated head backward (lv_enc_head_gated_bwd_f32, or
+        lv_reparam_kl_gated_bwd_f32 beyond the one-launch head).  loss_sum reports the objective that was minimised (the inner
+        loop's exit test reads it), kl_sum the analytic, unthresholded KL; st.kl_obj [B] and st.kl_gate [B][nz] of a shape's step
+        state hold the last step's thresholded KL and gate.  Not implemented together with objective = "iw" (no analytic KL term),
+        grad_sync or micro_batches > 1 (a batch statistic would have to cross ranks or slices).
+        objective = "elbo" (default: rec averaged over the samples + kl_weight * analytic KL, VAE.loss) or "iw": the step minimises
         the importance-weighted bound -(logsumexp_s log w_s - log ns) that VAE.nll_iw(x, ns, ns) estimates (vae.py:100-129; kl_weight
         scales log q - log p inside log w, 1 is the reference's), differentiated through the reparameterised samples: the decoder rows
         are seeded with g * softmax_s(log w) instead of g / ns and the encoder head takes per-sample terms instead of the analytic-KL
@@ -134,6 +145,15 @@ class AggressiveTextTrainer(object):
         if objective not in ("elbo", "iw"):
             raise ValueError("objective: 'elbo' or 'iw', not %r" % (objective,))
         self.objective = objective
+        self.free_bits = None
+        self.free_bits_mode = free_bits_mode
+        if free_bits is not None:
+            self.free_bits, self._fb_mode = _eng.check_free_bits(free_bits, free_bits_mode)
+            fenced = [n for n, on in (("objective='iw'", objective == "iw"), ("grad_sync", grad_sync is not None),
+                                      ("micro_batches > 1", self.micro_batches > 1)) if on]
+            if fenced:
+                raise ValueError("free_bits runs on a single GPU with micro_batches = 1 under objective = 'elbo'; not implemented "
+                                 "together with: %s" % ", ".join(fenced))
         if self.nsamples > 1 or objective == "iw":
             fenced = [n for n, on in (("grad_sync", grad_sync is not None), ("use_graph=True", bool(use_graph)),
                                       ("micro_batches > 1", self.micro_batches > 1), ("decoder_grads='norm'", decoder_grads == "norm")) if on]
@@ -391,6 +411,9 @@ class AggressiveTextTrainer(object):
             if self.objective == "iw":
                 st.wz = torch.empty(B, ns, dtype=torch.float32, device=d)                # beta * g * softmax_s(log w): the head's seeds
                 st.logw = torch.empty(B, ns, dtype=torch.float32, device=d)
+            if self.free_bits is not None:
+                st.kl_obj = torch.empty(B, dtype=torch.float32, device=d)                # the thresholded KL of the last step
+                st.kl_gate = torch.empty(B, nz, dtype=torch.float32, device=d)           # its gate, 0.0 / 1.0
             st.dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
             st.graphs = {}
             st.x_key = None
@@ -426,13 +449,25 @@ class AggressiveTextTrainer(object):
         m_out = st.m_out if use_out else None
         # encoder: ... LSTM, then head + reparameterise + KL in one launch
         mulv = self.enc.forward(st.xin, head=(st.eps, st.z, st.kl), x_key=st.x_key)
+        if self.free_bits is not None:
+            # free bits: the compared statistic, the gate and the thresholded KL of this step, one launch
+            lib.lv_kl_freebits_fwd_f32(P(mulv), self.free_bits, self._fb_mode, P(st.kl_obj), P(st.kl_gate), None, B, st.eps.shape[2], s)
         self.dec.forward(st.xin, st.z, m_in, m_out, dec.dropout_in.p, dec.dropout_out.p, want_rec=False, x_key=st.x_key)
         ns = self.nsamples
         w = self.dec._ws(B * ns, T - 1, ns)
         # rec, loss, the running report sums and the seeds of mean_b(loss_b).backward(), one launch
         # (report sums into the pending slots: committed by the transaction gate; the Philox offset moves on here when drawn)
         iw = self.objective == "iw"
-        if iw:
+        fb = self.free_bits is not None
+        if fb:
+            # free bits: the assembly takes kl_obj into the loss and leaves the analytic KL in the report sum
+            a = (P(w.nll), P(st.kl), P(st.kl_obj), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
+                 self._s(10), T - 1, B, ns)
+            if draw:
+                lib.lv_loss_assemble_fb_rng_f32(*a, P(self.rng_state), 1, s)
+            else:
+                lib.lv_loss_assemble_fb_f32(*a, s)
+        elif iw:
             a = (P(w.nll), P(mulv), P(st.eps), P(st.z), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec),
                  P(st.rowscale), P(st.wz), P(st.logw), self._s(10), T - 1, B, ns, st.eps.shape[2])
             if draw:
@@ -483,6 +518,8 @@ class AggressiveTextTrainer(object):
             else:
                 start()                   # step kernels: the collective runs under the whole encoder backward
         head = (st.eps, dzp, parts, st.wz, "iw") if iw else (st.eps, dzp, parts, st.dkl)
+        if fb:
+            head = (st.eps, dzp, parts, st.dkl, st.kl_gate)
         self.enc.backward(None, head=head, after_bptt=hook, after_embed=bucket)
         self.dec.join()           # decoder weight-gradient GEMMs ran on the side stream underneath the BPTT chains
         if self.grad_sync is not None and self.grad_sync.active:
@@ -891,7 +928,8 @@ class SemiAmortizedTextTrainer(AggressiveTextTrainer):
                                   ("micro_batches > 1", int(kw.get("micro_batches", 1)) > 1),
                                   ("decoder_grads='norm'", kw.get("decoder_grads", "full") != "full"),
                                   ("fold_norm=True", bool(kw.get("fold_norm", False))),
-                                  ("objective='iw'", kw.get("objective", "elbo") != "elbo")) if on]
+                                  ("objective='iw'", kw.get("objective", "elbo") != "elbo"),
+                                  ("free_bits", kw.get("free_bits") is not None)) if on]
         if fenced:
             raise ValueError("semi-amortized training runs on a single GPU in eager mode with micro_batches = 1, decoder_grads = "
                              "'full' and fold_norm off; not implemented together with: %s" % ", ".join(fenced))
@@ -969,10 +1007,21 @@ class AggressiveImageTrainer(object):
     nsamples = ns > 1 (image.py --nsamples: VAE.loss(x, kl_weight, nsamples=ns)): the encoder runs on the B images, ns latent samples
     are drawn per image, the decoder runs on B*ns images in the reference's row order b*ns + s (dec_pixelcnn_v2.py:178-190; BatchNorm
     batch statistics over all B*ns of them) reading each image's pixels from the one copy of x, and the reconstruction term of an
-    image is the mean over its samples.  read_stats() sums stay sums over the B images."""
+    image is the mean over its samples.  read_stats() sums stay sums over the B images.
+
+    free_bits = lambda >= 0 (None: off, the step's launches unchanged), free_bits_mode "dim" / "batch_dim" / "batch": the free-bits
+    objective of AggressiveTextTrainer -- lv_kl_freebits_fwd_f32 behind lv_reparam_kl_fwd_f32, lv_loss_assemble_fb_f32
+    and lv_reparam_kl_gated_bwd_f32, for ns = 1 and ns > 1, eager and hipGraph; loss_sum is the objective, kl_sum the analytic KL;
+    self.kl_obj [B] / self.kl_gate [B][nz] hold the last step's thresholded KL and gate."""
 
     def __init__(self, vae, lr=1e-3, clip=5.0, seed=783435, device=None, precision="f32", betas=(0.9, 0.999), eps=1e-8,
-                 use_graph=False, nsamples=1):
+                 use_graph=False, nsamples=1, free_bits=None, free_bits_mode="dim"):
+        self.free_bits = None
+        self.free_bits_mode = free_bits_mode
+        self._fb_state = {}
+        self.kl_obj = self.kl_gate = None
+        if free_bits is not None:
+            self.free_bits, self._fb_mode = _eng.check_free_bits(free_bits, free_bits_mode)
         if isinstance(nsamples, bool) or not isinstance(nsamples, int) or nsamples < 1:
             raise ValueError("nsamples must be an integer >= 1, not %r" % (nsamples,))
         self.nsamples = nsamples
@@ -1143,7 +1192,19 @@ class AggressiveImageTrainer(object):
         gl = torch.full((B,), 1.0 / B, dtype=torch.float32, device=d)
         drec = torch.empty(B * ns, dtype=torch.float32, device=d)
         dkl = torch.empty(B, dtype=torch.float32, device=d)
-        if ns == 1:
+        gate = None
+        if self.free_bits is not None:
+            # free bits: gate and thresholded KL in one launch, kl_obj in the loss, the analytic KL in the report sum
+            # (one pair of buffers per batch size, made by the first -- eager -- body: a captured graph writes the same ones, so that
+            #  they hold the last step's values after a warm-up as after a replay)
+            if B not in self._fb_state:
+                self._fb_state[B] = (torch.empty(B, dtype=torch.float32, device=d), torch.empty(B, nz, dtype=torch.float32, device=d))
+            kl_obj, gate = self._fb_state[B]
+            lib.lv_kl_freebits_fwd_f32(P(mulv), self.free_bits, self._fb_mode, P(kl_obj), P(gate), None, B, nz, s)
+            lib.lv_loss_assemble_fb_f32(P(rec), P(kl), P(kl_obj), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(dkl), self._s(5), 1, B,
+                                        ns, s)
+            self.kl_obj, self.kl_gate = kl_obj, gate
+        elif ns == 1:
             # (lv_loss_assemble_ns_f32 sums scal[5..7] in another order than lv_sum_accum_f32: the single-sample step keeps its chain,
             # and with it its bits)
             lib.lv_vae_loss_f32(P(rec), P(kl), self._s(0), P(loss), P(rec2), 1, B, s)
@@ -1157,7 +1218,10 @@ class AggressiveImageTrainer(object):
             lib.lv_loss_assemble_ns_f32(P(rec), P(kl), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(dkl), self._s(5), 1, B, ns, s)
         dz = self.dec.backward(drec)
         dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
-        lib.lv_reparam_kl_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(dmulv), B, ns, nz, s)
+        if gate is not None:
+            lib.lv_reparam_kl_gated_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(gate), P(dmulv), B, ns, nz, s)
+        else:
+            lib.lv_reparam_kl_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(dmulv), B, ns, nz, s)
         self.enc.backward(dmulv)
         ef, df = self.enc.flat, self.dec.flat
         lib.lv_sumsq_f32(P(ef.grad), ef.numel, P(self.norm_ws), self._s(2), 0, s)

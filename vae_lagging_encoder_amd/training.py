@@ -62,9 +62,24 @@ def _objective(args, trainer):
     return objective
 
 
+def _free_bits(args, trainer):
+    """(args.free_bits, args.free_bits_mode) -- (None, "dim") when the fields are missing: the free-bits objective of the TRAINING
+    steps (AggressiveTextTrainer / AggressiveImageTrainer (free_bits=..., free_bits_mode=...)); the evaluation passes
+    never apply it.  A trainer that is handed in must have been built with the same pair."""
+    fb, mode = getattr(args, "free_bits", None), getattr(args, "free_bits_mode", "dim")
+    if fb is not None:
+        fb = _eng.check_free_bits(fb, mode)[0]
+    if trainer is not None:
+        got = (getattr(trainer, "free_bits", None), getattr(trainer, "free_bits_mode", "dim"))
+        if got[0] != fb or (fb is not None and got[1] != mode):
+            raise ValueError("args.free_bits = %r (%s), but the trainer was built with free_bits = %r (%s)" % (fb, mode, got[0], got[1]))
+    return fb, mode
+
+
 class TextTrainingLoop(object):
     """args fields read (text.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
-    iw_nsamples, momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...)), and
+    iw_nsamples, free_bits / free_bits_mode (None / "dim" when missing: the free-bits objective of the training steps),
+    momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...)), and
     objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...)), and svi_steps (missing or 0: the ordinary steps;
     K > 0: semi-amortized training, SemiAmortizedTextTrainer, with svi_lr, svi_momentum, svi_clip and fd_eps)."""
 
@@ -87,6 +102,7 @@ class TextTrainingLoop(object):
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
         self.objective = _objective(args, trainer)
+        self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
         # args.svi_steps = K > 0: semi-amortized training (SemiAmortizedTextTrainer) with args.svi_lr, svi_momentum,
         # svi_clip and fd_eps (Kim et al.'s defaults when missing); missing or 0: the ordinary steps
         self.svi_steps = int(getattr(args, "svi_steps", 0) or 0)
@@ -95,6 +111,8 @@ class TextTrainingLoop(object):
         if self.svi_steps > 0 and (bool(args.aggressive) or self.objective == "iw"):
             raise ValueError("args.svi_steps = %d (semi-amortized training) runs neither with aggressive = 1 nor with objective = 'iw'"
                              % self.svi_steps)
+        if self.svi_steps > 0 and self.free_bits is not None:
+            raise ValueError("args.free_bits is not implemented together with args.svi_steps > 0 (semi-amortized training)")
         if self.svi_steps > 0 and trainer is None:
             trainer = SemiAmortizedTextTrainer(vae, svi_steps=self.svi_steps, svi_lr=float(getattr(args, "svi_lr", 1.0)),
                                                svi_momentum=float(getattr(args, "svi_momentum", 0.5)),
@@ -102,7 +120,8 @@ class TextTrainingLoop(object):
                                                lr=1.0, clip=CLIP_GRAD, seed=seed, nsamples=self.nsamples, momentum=self.momentum)
         self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
                                                                                  nsamples=self.nsamples, momentum=self.momentum,
-                                                                                 objective=self.objective)
+                                                                                 objective=self.objective, free_bits=self.free_bits,
+                                                                                 free_bits_mode=self.free_bits_mode)
         if hasattr(self.trainer, "prepare_batches"):
             self.trainer.prepare_batches(train_batches)          # per-batch index structures, built once with the batch list
         self.rng = np_rng if np_rng is not None else np.random
@@ -258,8 +277,10 @@ class ImageTrainingLoop(object):
         self.nsamples = int(getattr(args, "nsamples", 1))
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
+        self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
         self.trainer = trainer if trainer is not None else AggressiveImageTrainer(vae, lr=self.LR0, clip=self.CLIP_GRAD, seed=seed,
-                                                                                  nsamples=self.nsamples)
+                                                                                  nsamples=self.nsamples, free_bits=self.free_bits,
+                                                                                  free_bits_mode=self.free_bits_mode)
         self.rng = np_rng if np_rng is not None else np.random
         self.binarize_fn, self.eps_fn, self.epoch_hook = binarize_fn, eps_fn, epoch_hook
         self.decay_epoch = self.DECAY_EPOCH if decay_epoch is None else decay_epoch
@@ -429,8 +450,10 @@ class ToyTrainingLoop(object):
         self.single = args.plot_mode == "single"
         self.opt = {"not_improved": 0, "lr": self.LR0[self.optim], "best_loss": 1e4}
         self.objective = _objective(args, trainer)
+        self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
         if trainer is None:
-            trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim, objective=self.objective)
+            trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim, objective=self.objective,
+                                            free_bits=self.free_bits, free_bits_mode=self.free_bits_mode)
         elif getattr(trainer, "optimizer", "sgd") != self.optim:
             raise ValueError("args.optim is %r but the trainer steps with %r" % (self.optim, getattr(trainer, "optimizer", "sgd")))
         self.trainer = trainer
