@@ -380,6 +380,23 @@ int lv_loss_assemble_iw_rng_f32(const float* nll, const float* mulv, const float
 /* the weights' direct gradient for the autograd route (dz itself travels through lv_reparam_kl_bwd_f32): dmulv [B][2nz] ('='),
  * dmu_j = sum_s c_s z_sj, dlogvar_j = sum_s c_s z_sj eps_sj sigma_j / 2 - sum_s c_s / 2, c = wz [B][ns] */
 int lv_reparam_iw_bwd_f32(const float* mulv, const float* eps, const float* wz, float* dmulv, int B, int ns, int nz, void* stream);
+/* the doubly-reparameterised estimator of the same objective (DReG, Tucker et al. 2019): every output of
+ * lv_loss_assemble_iw_f32 bit for bit except wz, plus rs [B][ns] = r_s = 1 - w*(1 - wn_s) (exactly 1 at wn_s = 1, so at ns = 1) and
+ * wz[b][s] = c'_s = (w*rowscale[b*ns + s])*r_s = w*g*u_s with u_s = (1 - w)*wn_s + w*wn_s^2. */
+int lv_loss_assemble_dreg_f32(const float* nll, const float* mulv, const float* eps, const float* z, const float* kl,
+                              const float* kl_weight_dev, const float* g_loss, float* loss, float* rec, float* rowscale,
+                              float* wz, float* rs, float* logw, float* acc_dev, int T, int B, int ns, int nz, void* stream);
+int lv_loss_assemble_dreg_rng_f32(const float* nll, const float* mulv, const float* eps, const float* z, const float* kl,
+                                  const float* kl_weight_dev, const float* g_loss, float* loss, float* rec, float* rowscale,
+                                  float* wz, float* rs, float* logw, float* acc_dev, int T, int B, int ns, int nz,
+                                  uint64_t* rng_state, uint64_t rng_inc, void* stream);
+/* the complete dmulv [B][2nz] ('=') from the decoder's dz [B][ns][nz] (carrying g*wn_s), one launch, one thread per (b, j), serial
+ * over s.  rs == NULL (wz = c of lv_loss_assemble_iw_f32): t_sj = dz_sj + c_s z_sj, dmu_j = sum_s t_sj,
+ * dlogvar_j = sum_s t_sj eps_sj sigma_j / 2 - sum_s c_s / 2; with wz all zeros the bits of lv_reparam_kl_bwd_f32 with dkl all zeros.
+ * rs != NULL (wz = c', rs = r of lv_loss_assemble_dreg_f32): t_sj = r_s dz_sj + c'_s (z_sj - eps_sj exp(-logvar_j/2)),
+ * dmu_j = sum_s t_sj, dlogvar_j = sum_s t_sj eps_sj sigma_j / 2. */
+int lv_reparam_iwdz_bwd_f32(const float* mulv, const float* eps, const float* dz, const float* wz, const float* rs, float* dmulv,
+                            int B, int ns, int nz, void* stream);
 
 /* ---- the free-bits (KL thresholding) objective (lv_freebits.hip; Kingma et al. 2016, Chen et al. 2017, Li et al. 2019) ----
  * Per sentence b and latent dimension j, KL_bj = 0.5 (mu_bj^2 + exp(lv_bj) - lv_bj - 1).  lam = free_bits >= 0, in nats PER LATENT
@@ -428,6 +445,12 @@ int lv_enc_head_bwd_f32(const float* mulv, const float* eps, const float* dz, in
 int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz,
                            const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin, int B, int H, int ns,
                            int nz, void* stream);
+/* the same under the doubly-reparameterised estimator: wz = c', rs = r [B][ns] of lv_loss_assemble_dreg_f32, the per-sample terms of
+ * lv_reparam_iwdz_bwd_f32 with rs != NULL.  With wz all zeros and rs all ones the three outputs are bit-identical to
+ * lv_enc_head_bwd_f32 with dkl all zeros.  rs is read from global memory: the LDS envelope is lv_enc_head_bwd_f32's. */
+int lv_enc_head_dreg_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz, const float* rs,
+                             const float* hT, const float* w_lin, float* dmulv, float* dhT, float* gw_lin, int B, int H, int ns,
+                             int nz, void* stream);
 /* lv_enc_head_bwd_f32 under free bits: dkl[b] * gate[b][j] (gate [B][nz] of lv_kl_freebits_fwd_f32) in place of dkl[b].  With a
  * gate of all ones every output is bit-identical to lv_enc_head_bwd_f32's. */
 int lv_enc_head_gated_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* dkl,

@@ -62,6 +62,10 @@ SIGNATURES = {
     "lv_loss_assemble_iw_rng_f32": [_vp] * 13 + [_i, _i, _i, _i, _vp, _u64, _vp],
     "lv_reparam_iw_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_enc_head_iw_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "lv_loss_assemble_dreg_f32": [_vp] * 14 + [_i, _i, _i, _i, _vp],
+    "lv_loss_assemble_dreg_rng_f32": [_vp] * 14 + [_i, _i, _i, _i, _vp, _u64, _vp],
+    "lv_reparam_iwdz_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "lv_enc_head_dreg_bwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "lv_kl_freebits_fwd_f32": [_vp, _f, _i, _vp, _vp, _vp, _i, _i, _vp],
     "lv_reparam_kl_gated_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "lv_loss_assemble_fb_f32": [_vp] * 10 + [_i, _i, _i, _vp],

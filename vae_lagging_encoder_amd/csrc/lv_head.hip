@@ -108,8 +108,13 @@ __device__ __forceinline__ const float* head_gate(const float* g) { return g; }
 // every operation reduces to the one the plain kernel does with dkl all zeros: the same bits.
 // GATED (free bits, lv_freebits.hip): the analytic-KL seed of dimension j is dkl_b * gate_bj, gate [B][nz] of 0.0f / 1.0f;
 // with a gate of all ones the product is dkl_b itself: the same bits.
-// The gate travels as a trailing parameter pack (empty, or one `const float*`): the ungated kernels keep their argument list.
-template <int HB_COLS, bool IW, class... Gate>
+// DREG (the doubly-reparameterised estimator of "iw"): `dkl` is wz [B][ns] = c'_s and the pack carries rs [B][ns] = r_s:
+// t_sj = r_s dz_sj + c'_s (z_sj - eps_sj exp(-logvar_j/2)), dmu_j = sum_s t_sj, dlogvar_j = sum_s t_sj 1/2 eps_sj sigma_j.  rs and wz
+// are read from global memory (B*ns floats, each read by the nz threads of its row: cache hits), not staged: the LDS budget of
+// engine.fused_ends_ok is the other modes'.  With wz all zeros and rs all ones t_sj = dz_sj: the plain kernel's bits at dkl = 0.
+// The gate / rs travels as a trailing parameter pack (empty, or one `const float*`): the other kernels keep their argument list.
+enum { HEAD_PLAIN = 0, HEAD_IW = 1, HEAD_DREG = 2 };
+template <int HB_COLS, int MODE, class... Gate>
 __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restrict__ mulv, const float* __restrict__ eps,
                                                            const float* __restrict__ dz, int parts, const float* __restrict__ dkl,
                                                            const float* __restrict__ hT, const float* __restrict__ wlin,
@@ -180,7 +185,19 @@ __global__ __launch_bounds__(256) void enc_head_bwd_kernel(const float* __restri
         const float m = mulv[(long)bb * nz2 + j], lv = mulv[(long)bb * nz2 + nz + j];
         const float sdv = expf(0.5f * lv);
         float gz = 0.f, gze = 0.f, dm, dl;
-        if (IW) {
+        if constexpr (MODE == HEAD_DREG) {
+            const float* rsv = head_gate(gate...);
+            const float isd = expf(-0.5f * lv);
+            for (int s = 0; s < ns; ++s) {
+                const long zi = ((long)bb * ns + s) * nz + j;
+                const float e = eps[zi], c = dkl[(long)bb * ns + s], r = rsv[(long)bb * ns + s];
+                const float g = r * sg[zi] + c * ((m + e * sdv) - e * isd);
+                gz += g;
+                gze += g * e;
+            }
+            dm = gz;
+            dl = gze * (0.5f * sdv);
+        } else if (MODE == HEAD_IW) {
             float sc = 0.f;
             for (int s = 0; s < ns; ++s) {
                 const long zi = ((long)bb * ns + s) * nz + j;
@@ -355,7 +372,7 @@ extern "C" int lv_enc_head_bwd_f32(const float* mulv, const float* eps, const fl
     if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
     const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
     if ((base + per_col * 16) * sizeof(float) <= 64000)
-        LV_LAUNCH((enc_head_bwd_kernel<16, false>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
+        LV_LAUNCH((enc_head_bwd_kernel<16, HEAD_PLAIN>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
                   mulv, eps, dz, dz_parts, dkl, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz);
     else
         return LV_ERR_UNSUPPORTED;
@@ -373,8 +390,26 @@ extern "C" int lv_enc_head_iw_bwd_f32(const float* mulv, const float* eps, const
     if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
     const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
     if ((base + per_col * 16) * sizeof(float) <= 64000)
-        LV_LAUNCH((enc_head_bwd_kernel<16, true>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
+        LV_LAUNCH((enc_head_bwd_kernel<16, HEAD_IW>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256), (base + per_col * 16) * sizeof(float), stream,
                   mulv, eps, dz, dz_parts, wz, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz);
+    else
+        return LV_ERR_UNSUPPORTED;
+    LV_CHECK_LAUNCH();
+    return LV_OK;
+}
+
+// The same under the doubly-reparameterised estimator: wz [B][ns] = c'_s and rs [B][ns] = r_s from
+// lv_loss_assemble_dreg_f32.  With wz all zeros and rs all ones dmulv, dhT and gW_lin are bit-identical to lv_enc_head_bwd_f32 with
+// dkl all zeros.  Same LDS envelope as the other entries (rs is not staged).
+extern "C" int lv_enc_head_dreg_bwd_f32(const float* mulv, const float* eps, const float* dz, int dz_parts, const float* wz,
+                                        const float* rs, const float* hT, const float* wlin, float* dmulv, float* dhT, float* gwlin,
+                                        int B, int H, int ns, int nz, void* stream) {
+    if (!mulv || !eps || !dz || !wz || !rs || !hT || !wlin || !dmulv || !dhT || !gwlin) return LV_ERR_ARG;
+    if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
+    const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
+    if ((base + per_col * 16) * sizeof(float) <= 64000)
+        LV_LAUNCH((enc_head_bwd_kernel<16, HEAD_DREG, const float*>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256),
+                  (base + per_col * 16) * sizeof(float), stream, mulv, eps, dz, dz_parts, wz, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz, rs);
     else
         return LV_ERR_UNSUPPORTED;
     LV_CHECK_LAUNCH();
@@ -390,7 +425,7 @@ extern "C" int lv_enc_head_gated_bwd_f32(const float* mulv, const float* eps, co
     if (B <= 0 || H <= 0 || ns <= 0 || nz <= 0 || dz_parts <= 0) return LV_ERR_SHAPE;
     const size_t base = (size_t)B * 2 * nz + (size_t)B * ns * nz, per_col = (size_t)2 * nz + B;
     if ((base + per_col * 16) * sizeof(float) <= 64000)
-        LV_LAUNCH((enc_head_bwd_kernel<16, false, const float*>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256),
+        LV_LAUNCH((enc_head_bwd_kernel<16, HEAD_PLAIN, const float*>), dim3((unsigned)lv_cdiv(H, 16)), dim3(256),
                   (base + per_col * 16) * sizeof(float), stream, mulv, eps, dz, dz_parts, dkl, hT, wlin, dmulv, dhT, gwlin, B, H, ns, nz, gate);
     else
         return LV_ERR_UNSUPPORTED;

@@ -1304,7 +1304,9 @@ class LSTMEncoderEngine(object):
         head = (eps, dz [parts][B][ns][nz], parts, dkl [B]) instead of dmulv: the backward of reparameterise + KL runs in
         the head's launch (fused driver; dmulv is then produced into the workspace).  A fifth element "iw" selects the
         importance-weighted objective's head backward (lv_enc_head_iw_bwd_f32): the fourth is then wz [B][ns], the per-sample
-        seeds of lv_loss_assemble_iw_f32, in place of the analytic-KL seed.  A fifth element that is a tensor is the free-bits gate
+        seeds of lv_loss_assemble_iw_f32, in place of the analytic-KL seed; a fifth element "dreg" followed by rs [B][ns] selects
+        its doubly-reparameterised form (lv_enc_head_dreg_bwd_f32; wz and rs from lv_loss_assemble_dreg_f32; rs is read from global
+        memory, so the LDS budget of fused_ends_ok is unchanged).  A fifth element that is a tensor is the free-bits gate
         [B][nz] of lv_kl_freebits_fwd_f32: the analytic-KL seed of dimension j is then dkl[b] * gate[b][j] (lv_enc_head_gated_bwd_f32,
         or lv_reparam_kl_gated_bwd_f32 in front of the GEMM sequence beyond fused_ends_ok)."""
         x, B, T, g = self.last
@@ -1319,6 +1321,11 @@ class LSTMEncoderEngine(object):
         v, gv = f.views, f.gviews
         gate = head[4] if head is not None and len(head) == 5 and torch.is_tensor(head[4]) else None
         iw = head is not None and len(head) == 5 and gate is None and head[4] == "iw"
+        rs = head[5] if head is not None and len(head) == 6 and head[4] == "dreg" else None
+        if rs is not None:
+            iw = True
+            if not (rs.dtype == torch.float32 and rs.is_contiguous() and tuple(rs.shape) == tuple(head[3].shape)):
+                raise _lib.LvaeError("estimator 'dreg': rs is a contiguous float32 tensor of wz's shape")
         if head is not None:
             head = head[:4]
         if gate is not None and not (gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (B, nz2 // 2)):
@@ -1340,6 +1347,9 @@ class LSTMEncoderEngine(object):
             if gate is not None:
                 lib.lv_enc_head_gated_bwd_f32(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(gate), P(w.hs, T * B * H), P(v["linear.weight"]),
                                               P(w.dmulv), P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
+            elif rs is not None:
+                lib.lv_enc_head_dreg_bwd_f32(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(rs), P(w.hs, T * B * H), P(v["linear.weight"]),
+                                             P(w.dmulv), P(w.dhT), P(gv["linear.weight"]), B, H, eps.shape[1], nz2 // 2, s)
             else:
                 head_bwd = lib.lv_enc_head_iw_bwd_f32 if iw else lib.lv_enc_head_bwd_f32
                 head_bwd(P(w.mulv), P(eps), P(dz), parts, P(dkl), P(w.hs, T * B * H), P(v["linear.weight"]), P(w.dmulv),
@@ -2400,10 +2410,12 @@ def reparam_kl_gated_backward(mulv, eps, dz, dkl, gate):
     return dmulv
 
 
-def iw_assemble(rec_s, mulv, eps, z, kl, klw, g_loss, want_logw=False):
+def iw_assemble(rec_s, mulv, eps, z, kl, klw, g_loss, want_logw=False, rs=None):
     """Loss assembly of the importance-weighted objective on per-sample reconstruction errors (lv_loss_assemble_iw_f32 with T = 1):
     rec_s [B][ns], mulv [B][2nz], eps / z [B][ns][nz], kl / g_loss [B], klw: device float[1] -> loss [B], rec [B] (mean over the
-    samples), rowscale [B][ns] = g_loss * softmax_s(log w), wz [B][ns] = klw * rowscale, logw [B][ns] or None."""
+    samples), rowscale [B][ns] = g_loss * softmax_s(log w), wz [B][ns] = klw * rowscale, logw [B][ns] or None.
+    rs: a contiguous float32 [B][ns] tensor selects the doubly-reparameterised estimator (lv_loss_assemble_dreg_f32):
+    it is filled with r_s = 1 - klw * (1 - softmax_s(log w)) and wz is c'_s = klw * rowscale * r_s."""
     lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
     B, ns, nz = eps.shape
     f32 = dict(dtype=torch.float32, device=mulv.device)
@@ -2412,6 +2424,12 @@ def iw_assemble(rec_s, mulv, eps, z, kl, klw, g_loss, want_logw=False):
     rowscale, wz = torch.empty(B, ns, **f32), torch.empty(B, ns, **f32)
     logw = torch.empty(B, ns, **f32) if want_logw else None
     acc = torch.zeros(3, **f32)
+    if rs is not None:
+        if not (rs.dtype == torch.float32 and rs.is_contiguous() and tuple(rs.shape) == (B, ns) and rs.device == mulv.device):
+            raise ValueError("rs: a contiguous float32 (%d, %d) tensor on %s expected" % (B, ns, mulv.device))
+        lib.lv_loss_assemble_dreg_f32(*[P(a) for a in t], P(loss), P(rec), P(rowscale), P(wz), P(rs), P(logw) if want_logw else None,
+                                      P(acc), 1, B, ns, nz, s)
+        return loss, rec, rowscale, wz, logw
     lib.lv_loss_assemble_iw_f32(*[P(a) for a in t], P(loss), P(rec), P(rowscale), P(wz), P(logw) if want_logw else None, P(acc),
                                 1, B, ns, nz, s)
     return loss, rec, rowscale, wz, logw
@@ -2424,6 +2442,18 @@ def reparam_iw_backward(mulv, eps, wz):
     dmulv = torch.empty_like(mulv)
     mulv_c, eps_c, wz_c = mulv.contiguous(), eps.contiguous(), wz.contiguous()
     lib.lv_reparam_iw_bwd_f32(P(mulv_c), P(eps_c), P(wz_c), P(dmulv), B, ns, nz, s)
+    return dmulv
+
+
+def reparam_iwdz_backward(mulv, eps, dz, wz, rs=None):
+    """The complete gradient to [mu | logvar] of the importance-weighted objective from the decoder's dz [B][ns][nz]
+    (lv_reparam_iwdz_bwd_f32); wz [B][ns] from iw_assemble; rs [B][ns]: its doubly-reparameterised form (wz is then c')."""
+    lib, s = backend_for(mulv.device), stream_ptr(mulv.device)
+    B, ns, nz = eps.shape
+    dmulv = torch.empty_like(mulv)
+    t = [a.contiguous() for a in (mulv, eps, dz, wz)]
+    rs_c = None if rs is None else rs.contiguous()
+    lib.lv_reparam_iwdz_bwd_f32(*[P(a) for a in t], None if rs_c is None else P(rs_c), P(dmulv), B, ns, nz, s)
     return dmulv
 
 

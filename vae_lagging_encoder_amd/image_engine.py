@@ -140,11 +140,17 @@ class Tape(object):
         """The pending summands of the gradient of `act` (a list of 1..4 tensors in arrival order), or None."""
         return self.grads.get(id(act))
 
-    def backward(self):
+    def backward(self, retain=False):
+        """retain: the tape stays usable for another backward with other seeds (every gradient is written with '=', and the closures
+        keep no state of their own beyond self.grads, which the caller clears with reset_grads() once it has read what it needs)."""
         for fn in reversed(self.back):
             fn()
-        self.back = []
+        if not retain:
+            self.back = []
         self.flush_wgrads()
+
+    def reset_grads(self):
+        self.grads = {}
 
     def flush_wgrads(self):
         """Sum the weight-gradient partials of every direct convolution of this backward pass in one launch
@@ -600,6 +606,7 @@ class ImageDecoderEngine(object):
         self.bn_partial_cap = _BN_MAX_BLOCKS      # see Tape: partial rows past which a BatchNorm's statistics are finished by their own launch
         self.launches = {"bn_finish_fwd": 0, "bn_finish_bwd": 0}
         self.ns = 1               # samples per image of the last forward()
+        self.retain_tape = False  # True: backward() leaves the tape in place for another backward (set around a nested pass)
         self.gen = 0
         self.wgen = 0             # bumped by the fused trainer after a raw-pointer weight update
         self._wcache = {}
@@ -649,10 +656,13 @@ class ImageDecoderEngine(object):
         self.gen += 1
         return self.rec
 
-    def backward(self, drec, gen=None):
-        """drec [B*ns] -> parameter grads in self.flat.grad; returns dz [B*ns, nz]."""
+    def backward(self, drec, gen=None, retain=False):
+        """drec [B*ns] -> parameter grads in self.flat.grad ('='); returns dz [B*ns, nz].  retain (or self.retain_tape): the
+        activations stay for another backward with other seeds -- the decoder's BatchNorm couples the rows of a batch, so the
+        doubly-reparameterised estimator needs dz under the seeds g * u_s and the parameter gradients under g * wn_s."""
         if gen is not None and gen != self.gen:
             raise _lib.LvaeError("decoder activations were overwritten by a later forward()")
+        retain = retain or self.retain_tape
         tp = self.tape
         B = self.rec.shape[0]
         dlogit = tp.f32(B * 28 * 28, 1)
@@ -663,8 +673,11 @@ class ImageDecoderEngine(object):
         else:
             tp.lib.lv_sigmoid_bce_ns_bwd_f32(P(self.logit.t), P(self.xflat), P(drec_c), P(dlogit), B // ns, ns, 28 * 28, 1e-12, tp.s())
         tp.add_grad(self.logit, dlogit)
-        tp.backward()
-        return tp.grad_of(self.zact)
+        tp.backward(retain=retain)
+        dz = tp.grad_of(self.zact)
+        if retain:
+            tp.reset_grads()
+        return dz
 
 
 def _gemm_f32_split(M, N, K, ws_floats):

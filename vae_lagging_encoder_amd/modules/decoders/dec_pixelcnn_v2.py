@@ -181,6 +181,11 @@ class PixelCNNDecoderV2(DecoderBase):
             nn.init.zeros_(lin.bias)
         _unit_affine_(self.main[2])
 
+    def couples_samples(self):
+        """True when rec of one row depends on the z of the others: BatchNorm in train mode normalises with the statistics of all
+        batch * n_sample decoder images (VAE.loss_iw(estimator="dreg") then takes two backward passes)."""
+        return bool(self.training)
+
     def reconstruct_error(self, x, z, masks=None):
         """Binary cross entropy summed over pixels.  x (batch, 1, 28, 28) in {0,1}, z (batch, n_sample, nz)
         -> (batch, n_sample)."""

@@ -20,22 +20,60 @@ _GENERATORS = {"beam": "beam_search_decode", "greedy": "greedy_decode", "sample"
 class _IWBoundFn(torch.autograd.Function):
     """(rec_s [B][ns], mulv) -> (loss [B], rec [B]) of the importance-weighted bound (lv_loss_assemble_iw_f32 on T = 1).  z enters as
     data: its gradient through the decoder arrives with rec_s (seeded with g * softmax_s(log w)), the weights' direct dependence on
-    z = mu + eps * sigma and on logvar goes straight to mulv (lv_reparam_iw_bwd_f32)."""
+    z = mu + eps * sigma and on logvar goes straight to mulv (lv_reparam_iw_bwd_f32).
+    rs [B][ns] (estimator "dreg"): the forward fills it with r_s = 1 - kl_weight * (1 - wn_s) -- _ScaleSamplesFn, which
+    sits on z in front of the decoder, reads it in its backward -- and the direct terms are the doubly-reparameterised ones
+    (lv_loss_assemble_dreg_f32; lv_reparam_iwdz_bwd_f32 on dz = 0)."""
 
     @staticmethod
-    def forward(ctx, rec_s, mulv, eps, z, kl, klw):
+    def forward(ctx, rec_s, mulv, eps, z, kl, klw, rs=None, hold=None):
         one = torch.ones(mulv.shape[0], dtype=torch.float32, device=mulv.device)
-        loss, rec, _, _, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, one)
+        loss, rec, _, _, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, one, rs=rs)
         ctx.save_for_backward(rec_s, mulv, eps, z, kl, klw)
+        ctx.dreg = rs is not None
+        ctx.hold = hold
         ctx.mark_non_differentiable(rec)
         return loss, rec
 
     @staticmethod
     def backward(ctx, dloss, drec):
         rec_s, mulv, eps, z, kl, klw = ctx.saved_tensors
+        if ctx.dreg:
+            # r_s does not depend on the seed: this launch rewrites the forward's values into a buffer of its own
+            rs = torch.empty_like(rec_s, memory_format=torch.contiguous_format)
+            _, _, rowscale, wz, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, dloss, rs=rs)
+            hold = ctx.hold
+            if hold is not None:
+                # a decoder that couples the rows (train-mode BatchNorm): what reaches z is the decoder's backward under the seeds
+                # g * u_s = rowscale * r, a pass of its own through the decoder's graph, run here -- before the outer backward walks
+                # that graph with the seeds g * wn_s for the decoder's parameters -- and handed to _ScaleSamplesFn
+                eng = hold["engine"]
+                eng.retain_tape = True
+                try:
+                    hold["dz"] = torch.autograd.grad(rec_s, hold["zs"], rowscale * rs, retain_graph=True)[0]
+                finally:
+                    eng.retain_tape = False
+            return rowscale, _eng.reparam_iwdz_backward(mulv, eps, torch.zeros_like(eps), wz, rs), None, None, None, None, None, None
         # the same launch with the incoming gradient as seed: rowscale = dloss * wn, wz = kl_weight * rowscale
         _, _, rowscale, wz, _ = _eng.iw_assemble(rec_s, mulv, eps, z, kl, klw, dloss)
-        return rowscale, _eng.reparam_iw_backward(mulv, eps, wz), None, None, None, None
+        return rowscale, _eng.reparam_iw_backward(mulv, eps, wz), None, None, None, None, None, None
+
+
+class _ScaleSamplesFn(torch.autograd.Function):
+    """Identity on z [B][ns][nz]; the backward multiplies the gradient of sample s by rs[b][s], read when the backward runs (the
+    doubly-reparameterised estimator: only what flows from z into (mu, logvar) is rescaled, the decoder's parameters see the
+    unscaled seeds)."""
+
+    @staticmethod
+    def forward(ctx, z, rs, hold=None):
+        ctx.rs, ctx.hold = rs, hold
+        return z.view_as(z)
+
+    @staticmethod
+    def backward(ctx, dz):
+        if ctx.hold is not None:              # a row-coupling decoder: dz under the seeds g * u_s, made by _IWBoundFn.backward
+            return ctx.hold.pop("dz"), None, None
+        return dz * ctx.rs.unsqueeze(-1), None, None
 
 
 class _SAVAEFn(torch.autograd.Function):
@@ -261,23 +299,40 @@ class VAE(nn.Module):
         rec = self.decoder.reconstruct_error(x, z, **dec_extra).mean(dim=1)
         return rec + kl_weight * kl, rec, kl
 
-    def loss_iw(self, x, kl_weight=1.0, nsamples=1, noise=None):
+    def loss_iw(self, x, kl_weight=1.0, nsamples=1, noise=None, estimator="iwae"):
         """The importance-weighted bound as a training objective -> (loss, rec, KL), each (batch,):
         loss = -(logsumexp_s log w_s - log nsamples), log w_s = log p(x|z_s) + kl_weight * (log p(z_s) - log q(z_s|x)) -- with
         kl_weight = 1 what nll_iw(x, nsamples, nsamples) estimates (reference vae.py:100-129) -- differentiable through the
         reparameterised samples; rec is the sample mean of the reconstruction error and KL the analytic one, both for reports only
         (detached).  nsamples = 1 is a single-sample Monte-Carlo ELBO: its KL term is the sampled log q - log p, not the analytic KL.
-        Works with every decoder that has reconstruct_error(x, z) -> (batch, nsamples).  noise: as `loss`."""
+        Works with every decoder that has reconstruct_error(x, z) -> (batch, nsamples).  noise: as `loss`.
+        estimator = "dreg": the doubly-reparameterised estimator of the encoder's gradient (Tucker et al. 2019) --
+        the same three values and the same decoder gradient; what flows from z_s into (mu, logvar) is scaled by
+        r_s = 1 - kl_weight * (1 - wn_s) and the weights' direct terms take their doubly-reparameterised form.  A decoder whose rows
+        are coupled (decoder.couples_samples(): the PixelCNN decoder's BatchNorm in train mode) gets a second backward pass, seeded
+        with g * u_s, for what reaches z; its parameters still receive the gradient of the g * wn_s pass."""
         from .encoders.encoder import _ReparamKLFn
+        if estimator not in ("iwae", "dreg"):
+            raise ValueError("estimator: 'iwae' or 'dreg', not %r" % (estimator,))
         eps, masks = (None, None) if noise is None else (noise[0], (noise[1], noise[2]))
         x = self._batch(x)
         mulv = self.encoder._forward_mulv(x)
         eps = self.encoder._draw_eps(mulv.shape[0], nsamples, mulv.shape[1] // 2, mulv.device, eps)
         z, kl = _ReparamKLFn.apply(mulv, eps)
         dec_extra = {} if masks is None else {"masks": masks}
-        rec_s = self.decoder.reconstruct_error(x, z, **dec_extra)
         klw = torch.full((1,), float(kl_weight), dtype=torch.float32, device=mulv.device)
-        loss, rec = _IWBoundFn.apply(rec_s, mulv, eps, z.detach(), kl.detach(), klw)
+        if estimator == "dreg":
+            rs = torch.empty(z.shape[0], z.shape[1], dtype=torch.float32, device=mulv.device)
+            coupled = getattr(self.decoder, "couples_samples", None)
+            hold = {"engine": self.decoder._hip} if coupled is not None and coupled() else None
+            zs = _ScaleSamplesFn.apply(z, rs, hold)
+            if hold is not None:
+                hold["zs"] = zs
+            rec_s = self.decoder.reconstruct_error(x, zs, **dec_extra)
+            loss, rec = _IWBoundFn.apply(rec_s, mulv, eps, z.detach(), kl.detach(), klw, rs, hold)
+            return loss, rec, kl.detach()
+        rec_s = self.decoder.reconstruct_error(x, z, **dec_extra)
+        loss, rec = _IWBoundFn.apply(rec_s, mulv, eps, z.detach(), kl.detach(), klw, None, None)
         return loss, rec, kl.detach()
 
     # True: loss_savae takes the decoder engine's semi-amortized step where _fused_savae_ok allows it; False forces the generic

@@ -66,6 +66,15 @@ def _log_demotion(rung):
           "%d (%s)" % (rung, _eng.PERSIST_RUNGS[rung]), file=sys.stderr)
 
 
+def _check_iw_estimator(objective, iw_estimator):
+    """The gradient estimator of objective "iw": "iwae" or "dreg" (DESIGN.md 3.3c); "elbo" has the one."""
+    if iw_estimator not in ("iwae", "dreg"):
+        raise ValueError("iw_estimator: 'iwae' or 'dreg', not %r" % (iw_estimator,))
+    if iw_estimator != "iwae" and objective != "iw":
+        raise ValueError("iw_estimator = %r is an estimator of objective = 'iw', not of %r" % (iw_estimator, objective))
+    return iw_estimator
+
+
 class AggressiveTextTrainer(object):
     # data parallel: the embedding gradient goes out as its own all-reduce bucket when it has at least this many elements
     # (below ~4 MB a second collective costs more in latency than its overlap buys)
@@ -74,8 +83,12 @@ class AggressiveTextTrainer(object):
     def __init__(self, vae, lr=1.0, clip=5.0, seed=783435, grad_sync=None, use_graph=False, device=None,
                  precision="f32", micro_batches=1, fold_norm=True, decoder_grads="full", encoder_forward=None, forward_operands=None,
                  optimizer="sgd", betas=(0.9, 0.999), eps=1e-8, nsamples=1, momentum=0.0, objective="elbo", free_bits=None,
-                 free_bits_mode="dim"):
-        """free_bits = lambda >= 0 (nats per latent dimension; None: off, every launch of the step is the one it was): the step
+                 free_bits_mode="dim", iw_estimator="iwae"):
+        """iw_estimator = "iwae" (default: the reparameterised gradient of the bound) or "dreg" (objective "iw" only):
+        the doubly-reparameterised estimator of the encoder's gradient (Tucker et al. 2019) -- the same value, report
+        sums, log w and decoder gradient; the loss assembly also writes st.rs = r_s and the encoder head takes
+        lv_enc_head_dreg_bwd_f32's per-sample terms (lv_loss_assemble_dreg_f32).  Everything else is the "iw" step, fences included.
+        free_bits = lambda >= 0 (nats per latent dimension; None: off, every launch of the step is the one it was): the step
         minimises the free-bits objective rec + kl_weight * kl_obj (csrc/lv_freebits.hip), kl_obj the KL thresholded
         per free_bits_mode -- "dim" (each KL_bj against lambda), "batch_dim" (each dimension's batch mean against lambda) or "batch"
         (the batch mean of the whole KL against nz * lambda).  lambda and the mode are fixed at construction (launch constants, also
@@ -145,6 +158,7 @@ class AggressiveTextTrainer(object):
         if objective not in ("elbo", "iw"):
             raise ValueError("objective: 'elbo' or 'iw', not %r" % (objective,))
         self.objective = objective
+        self.iw_estimator = _check_iw_estimator(objective, iw_estimator)
         self.free_bits = None
         self.free_bits_mode = free_bits_mode
         if free_bits is not None:
@@ -411,6 +425,8 @@ class AggressiveTextTrainer(object):
             if self.objective == "iw":
                 st.wz = torch.empty(B, ns, dtype=torch.float32, device=d)                # beta * g * softmax_s(log w): the head's seeds
                 st.logw = torch.empty(B, ns, dtype=torch.float32, device=d)
+                if self.iw_estimator == "dreg":
+                    st.rs = torch.empty(B, ns, dtype=torch.float32, device=d)            # r_s = 1 - beta * (1 - softmax_s(log w)); wz is then c'
             if self.free_bits is not None:
                 st.kl_obj = torch.empty(B, dtype=torch.float32, device=d)                # the thresholded KL of the last step
                 st.kl_gate = torch.empty(B, nz, dtype=torch.float32, device=d)           # its gate, 0.0 / 1.0
@@ -468,12 +484,13 @@ class AggressiveTextTrainer(object):
             else:
                 lib.lv_loss_assemble_fb_f32(*a, s)
         elif iw:
+            dreg = self.iw_estimator == "dreg"
             a = (P(w.nll), P(mulv), P(st.eps), P(st.z), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec),
-                 P(st.rowscale), P(st.wz), P(st.logw), self._s(10), T - 1, B, ns, st.eps.shape[2])
+                 P(st.rowscale), P(st.wz)) + ((P(st.rs),) if dreg else ()) + (P(st.logw), self._s(10), T - 1, B, ns, st.eps.shape[2])
             if draw:
-                lib.lv_loss_assemble_iw_rng_f32(*a, P(self.rng_state), 1, s)
+                (lib.lv_loss_assemble_dreg_rng_f32 if dreg else lib.lv_loss_assemble_iw_rng_f32)(*a, P(self.rng_state), 1, s)
             else:
-                lib.lv_loss_assemble_iw_f32(*a, s)
+                (lib.lv_loss_assemble_dreg_f32 if dreg else lib.lv_loss_assemble_iw_f32)(*a, s)
         elif ns > 1 and draw:
             lib.lv_loss_assemble_ns_rng_f32(P(w.nll), P(st.kl), self._s(0), P(st.gl), P(st.loss), P(st.rec), P(st.rowscale), P(st.dkl),
                                             self._s(10), T - 1, B, ns, P(self.rng_state), 1, s)
@@ -518,6 +535,8 @@ class AggressiveTextTrainer(object):
             else:
                 start()                   # step kernels: the collective runs under the whole encoder backward
         head = (st.eps, dzp, parts, st.wz, "iw") if iw else (st.eps, dzp, parts, st.dkl)
+        if iw and self.iw_estimator == "dreg":
+            head = (st.eps, dzp, parts, st.wz, "dreg", st.rs)
         if fb:
             head = (st.eps, dzp, parts, st.dkl, st.kl_gate)
         self.enc.backward(None, head=head, after_bptt=hook, after_embed=bucket)
@@ -1012,10 +1031,28 @@ class AggressiveImageTrainer(object):
     free_bits = lambda >= 0 (None: off, the step's launches unchanged), free_bits_mode "dim" / "batch_dim" / "batch": the free-bits
     objective of AggressiveTextTrainer -- lv_kl_freebits_fwd_f32 behind lv_reparam_kl_fwd_f32, lv_loss_assemble_fb_f32
     and lv_reparam_kl_gated_bwd_f32, for ns = 1 and ns > 1, eager and hipGraph; loss_sum is the objective, kl_sum the analytic KL;
-    self.kl_obj [B] / self.kl_gate [B][nz] hold the last step's thresholded KL and gate."""
+    self.kl_obj [B] / self.kl_gate [B][nz] hold the last step's thresholded KL and gate.
+
+    objective = "iw" (default "elbo": the step above, launch for launch): the step minimises the importance-weighted bound
+    -(logsumexp_s log w_s - log ns) of AggressiveTextTrainer(objective="iw"): lv_loss_assemble_iw_f32 on T = 1
+    with the decoder's per-row rec as nll seeds the decoder backward with g * softmax_s(log w), and lv_reparam_iwdz_bwd_f32 forms the
+    whole dmulv from the decoder's dz.  Any nsamples >= 1, eager and hipGraph, every precision.  iw_estimator = "dreg": the
+    doubly-reparameterised estimator of the encoder's gradient (lv_loss_assemble_dreg_f32; the decoder's gradient is unchanged).  The
+    PixelCNN decoder's BatchNorm (train mode) couples the B*ns rows, so scaling dz_s by r_s is not enough here: the step runs the
+    decoder backward twice, seeded with g * u_s for dz and with g * wn_s for the parameters.
+    loss_sum reports the bound, rec_sum the sample mean of rec, kl_sum the analytic KL; self.logw [B][ns] holds the last step's log w.
+    Not implemented together with free_bits (no analytic KL term in the bound)."""
 
     def __init__(self, vae, lr=1e-3, clip=5.0, seed=783435, device=None, precision="f32", betas=(0.9, 0.999), eps=1e-8,
-                 use_graph=False, nsamples=1, free_bits=None, free_bits_mode="dim"):
+                 use_graph=False, nsamples=1, free_bits=None, free_bits_mode="dim", objective="elbo", iw_estimator="iwae"):
+        if objective not in ("elbo", "iw"):
+            raise ValueError("objective: 'elbo' or 'iw', not %r" % (objective,))
+        self.objective = objective
+        self.iw_estimator = _check_iw_estimator(objective, iw_estimator)
+        if objective == "iw" and free_bits is not None:
+            raise ValueError("free_bits runs under objective = 'elbo'; not implemented together with: objective='iw'")
+        self._iw_state = {}
+        self.logw = None
         self.free_bits = None
         self.free_bits_mode = free_bits_mode
         self._fb_state = {}
@@ -1204,6 +1241,19 @@ class AggressiveImageTrainer(object):
             lib.lv_loss_assemble_fb_f32(P(rec), P(kl), P(kl_obj), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(dkl), self._s(5), 1, B,
                                         ns, s)
             self.kl_obj, self.kl_gate = kl_obj, gate
+        elif self.objective == "iw":
+            # the importance-weighted bound on the decoder's per-row rec (T = 1): loss, rec2 = mean_s rec,
+            # scal[5..7] += sums, drec = g * softmax_s(log w) and the per-sample seeds wz (and rs under "dreg") in one launch
+            # (one set of buffers per batch size, made by the first -- eager -- body, as _fb_state: a captured graph writes the same)
+            dreg = self.iw_estimator == "dreg"
+            if B not in self._iw_state:
+                self._iw_state[B] = tuple(torch.empty(B, ns, dtype=torch.float32, device=d) for _ in range(4)) + \
+                    (torch.ones(B, ns, dtype=torch.float32, device=d),)
+            wz, rs, logw, drec_u, ones = self._iw_state[B]
+            a = (P(rec), P(mulv), P(eps), P(z), P(kl), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(wz)) + \
+                ((P(rs),) if dreg else ()) + (P(logw), self._s(5), 1, B, ns, nz, s)
+            (lib.lv_loss_assemble_dreg_f32 if dreg else lib.lv_loss_assemble_iw_f32)(*a)
+            self.logw = logw
         elif ns == 1:
             # (lv_loss_assemble_ns_f32 sums scal[5..7] in another order than lv_sum_accum_f32: the single-sample step keeps its chain,
             # and with it its bits)
@@ -1216,9 +1266,21 @@ class AggressiveImageTrainer(object):
             # rec2[b] = mean_s rec[b*ns + s], loss[b] = rec2[b] + w*kl[b], scal[5..7] += their sums over b, and the seeds of
             # loss.mean().backward(): drec[b*ns + s] = 1/(B*ns), dkl[b] = w/B -- one launch
             lib.lv_loss_assemble_ns_f32(P(rec), P(kl), self._s(0), P(gl), P(loss), P(rec2), P(drec), P(dkl), self._s(5), 1, B, ns, s)
-        dz = self.dec.backward(drec)
+        if self.objective == "iw" and dreg:
+            # The decoder's BatchNorm (train mode) couples the B*ns rows: d rec_s' / d z_s != 0, and the estimator weights every
+            # such term with u_s' = wn_s' r_s', not with r_s.  So dz comes from a backward of its own, seeded with g * u_s; the
+            # decoder's parameters then get the gradient they get under "iwae" from the usual backward (every gradient is written
+            # with '='), whose dz is dropped.  dz carries r already: the head terms take rs = 1.
+            torch.mul(drec, rs.view(-1), out=drec_u.view(-1))
+            dz = self.dec.backward(drec_u.view(-1), retain=True)
+            self.dec.backward(drec)
+        else:
+            dz = self.dec.backward(drec)
         dmulv = torch.empty(B, 2 * nz, dtype=torch.float32, device=d)
-        if gate is not None:
+        if self.objective == "iw":
+            # dz carries g * wn_s (g * u_s under "dreg") through the seeds; the weights' own terms in the same launch
+            lib.lv_reparam_iwdz_bwd_f32(P(mulv), P(eps), P(dz), P(wz), P(ones) if dreg else None, P(dmulv), B, ns, nz, s)
+        elif gate is not None:
             lib.lv_reparam_kl_gated_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(gate), P(dmulv), B, ns, nz, s)
         else:
             lib.lv_reparam_kl_bwd_f32(P(mulv), P(eps), P(dz), P(dkl), P(dmulv), B, ns, nz, s)

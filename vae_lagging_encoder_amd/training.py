@@ -62,6 +62,20 @@ def _objective(args, trainer):
     return objective
 
 
+def _iw_estimator(args, trainer, objective):
+    """args.iw_estimator ("iwae" when the attribute is missing; "dreg": the doubly-reparameterised estimator of objective "iw",
+    DESIGN.md 3.3c); a trainer that is handed in must have been built with the same one."""
+    est = getattr(args, "iw_estimator", "iwae")
+    if est not in ("iwae", "dreg"):
+        raise ValueError("args.iw_estimator: 'iwae' or 'dreg', not %r" % (est,))
+    if est != "iwae" and objective != "iw":
+        raise ValueError("args.iw_estimator = %r is an estimator of args.objective = 'iw', not of %r" % (est, objective))
+    if trainer is not None and getattr(trainer, "iw_estimator", "iwae") != est:
+        raise ValueError("args.iw_estimator = %r, but the trainer was built with iw_estimator = %r"
+                         % (est, getattr(trainer, "iw_estimator", "iwae")))
+    return est
+
+
 def _free_bits(args, trainer):
     """(args.free_bits, args.free_bits_mode) -- (None, "dim") when the fields are missing: the free-bits objective of the TRAINING
     steps (AggressiveTextTrainer / AggressiveImageTrainer (free_bits=..., free_bits_mode=...)); the evaluation passes
@@ -80,7 +94,8 @@ class TextTrainingLoop(object):
     """args fields read (text.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
     iw_nsamples, free_bits / free_bits_mode (None / "dim" when missing: the free-bits objective of the training steps),
     momentum (text.py --momentum: optim.SGD(lr, momentum) on both sides, AggressiveTextTrainer(momentum=...)), and
-    objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...)), and svi_steps (missing or 0: the ordinary steps;
+    objective ("elbo" when missing, or "iw": AggressiveTextTrainer(objective=...)), iw_estimator ("iwae" when missing, or "dreg"),
+    and svi_steps (missing or 0: the ordinary steps;
     K > 0: semi-amortized training, SemiAmortizedTextTrainer, with svi_lr, svi_momentum, svi_clip and fd_eps)."""
 
     def __init__(self, vae, train_batches, val_batches, test_batches, args, n_train_sentences=None, trainer=None,
@@ -102,6 +117,7 @@ class TextTrainingLoop(object):
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
         self.objective = _objective(args, trainer)
+        self.iw_estimator = _iw_estimator(args, trainer, self.objective)
         self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
         # args.svi_steps = K > 0: semi-amortized training (SemiAmortizedTextTrainer) with args.svi_lr, svi_momentum,
         # svi_clip and fd_eps (Kim et al.'s defaults when missing); missing or 0: the ordinary steps
@@ -121,7 +137,8 @@ class TextTrainingLoop(object):
         self.trainer = trainer if trainer is not None else AggressiveTextTrainer(vae, lr=1.0, clip=CLIP_GRAD, seed=seed,
                                                                                  nsamples=self.nsamples, momentum=self.momentum,
                                                                                  objective=self.objective, free_bits=self.free_bits,
-                                                                                 free_bits_mode=self.free_bits_mode)
+                                                                                 free_bits_mode=self.free_bits_mode,
+                                                                                 iw_estimator=self.iw_estimator)
         if hasattr(self.trainer, "prepare_batches"):
             self.trainer.prepare_batches(train_batches)          # per-batch index structures, built once with the batch list
         self.rng = np_rng if np_rng is not None else np.random
@@ -258,7 +275,9 @@ class ImageTrainingLoop(object):
       * the data come from shuffled DataLoaders (a fresh order for every pass, evaluation passes included), training batches
         are dynamically binarised (torch.bernoulli, image.py:287), validation / test batches are not.
     args fields read (image.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples (image.py --nsamples:
-    the trainer is built with it, AggressiveImageTrainer(nsamples=...), and the evaluation passes hand it to VAE.loss), test_nepoch.
+    the trainer is built with it, AggressiveImageTrainer(nsamples=...), and the evaluation passes hand it to VAE.loss), test_nepoch, objective ("elbo" when missing, or "iw":
+    AggressiveImageTrainer(objective=...)) and iw_estimator ("iwae" when missing, or "dreg") -- both concern the
+    training steps only: the evaluation passes are untouched.
 
     order_fn / binarize_fn / eps_fn inject the data order, the binarisation draw and the reparameterisation noise (parity replays
     of a recorded reference run); the defaults draw them as the reference's CPU path does / on the device.  eps_fn(x) returns
@@ -278,9 +297,15 @@ class ImageTrainingLoop(object):
         if trainer is not None and getattr(trainer, "nsamples", 1) != self.nsamples:
             raise ValueError("args.nsamples = %d, but the trainer was built with nsamples = %d" % (self.nsamples, getattr(trainer, "nsamples", 1)))
         self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
+        # args.objective / args.iw_estimator ("elbo" / "iwae" when missing): the objective of the TRAINING steps; the evaluation passes
+        # are the same for all of them
+        self.objective = _objective(args, trainer)
+        self.iw_estimator = _iw_estimator(args, trainer, self.objective)
         self.trainer = trainer if trainer is not None else AggressiveImageTrainer(vae, lr=self.LR0, clip=self.CLIP_GRAD, seed=seed,
                                                                                   nsamples=self.nsamples, free_bits=self.free_bits,
-                                                                                  free_bits_mode=self.free_bits_mode)
+                                                                                  free_bits_mode=self.free_bits_mode,
+                                                                                  objective=self.objective,
+                                                                                  iw_estimator=self.iw_estimator)
         self.rng = np_rng if np_rng is not None else np.random
         self.binarize_fn, self.eps_fn, self.epoch_hook = binarize_fn, eps_fn, epoch_hook
         self.decay_epoch = self.DECAY_EPOCH if decay_epoch is None else decay_epoch
@@ -421,7 +446,7 @@ class ToyTrainingLoop(object):
         test set in batches of one sentence).
     args fields read (toy.py's argparse names): kl_start, warm_up, batch_size, epochs, aggressive, nsamples, test_nepoch,
     iw_nsamples, optim, plot_mode, num_plot, plot_niter, zmin, zmax, dz, objective ("elbo" when missing, or "iw": the
-    single-sample importance-weighted step, AggressiveTextTrainer(objective="iw")).
+    single-sample importance-weighted step, AggressiveTextTrainer(objective="iw")), iw_estimator ("iwae" when missing, or "dreg").
 
     plot_data: the (batch, lengths) pair MonoTextData.data_sample returns (toy.py:304), or the batch tensor alone.
     noise_fn / epoch_hook / np_rng: as TextTrainingLoop's.  plot_dir: when given, every plot is also written as toy.py writes it
@@ -450,10 +475,11 @@ class ToyTrainingLoop(object):
         self.single = args.plot_mode == "single"
         self.opt = {"not_improved": 0, "lr": self.LR0[self.optim], "best_loss": 1e4}
         self.objective = _objective(args, trainer)
+        self.iw_estimator = _iw_estimator(args, trainer, self.objective)
         self.free_bits, self.free_bits_mode = _free_bits(args, trainer)
         if trainer is None:
             trainer = AggressiveTextTrainer(vae, lr=self.opt["lr"], clip=CLIP_GRAD, seed=seed, optimizer=self.optim, objective=self.objective,
-                                            free_bits=self.free_bits, free_bits_mode=self.free_bits_mode)
+                                            free_bits=self.free_bits, free_bits_mode=self.free_bits_mode, iw_estimator=self.iw_estimator)
         elif getattr(trainer, "optimizer", "sgd") != self.optim:
             raise ValueError("args.optim is %r but the trainer steps with %r" % (self.optim, getattr(trainer, "optimizer", "sgd")))
         self.trainer = trainer
