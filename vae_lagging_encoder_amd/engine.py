@@ -728,6 +728,37 @@ def _same_device(what, dev, **operands):
             raise _lib.LvaeError("%s: %s is on %s, x on %s" % (what, name, t.device, dev))
 
 
+def iters_per_launch_for(who, iters_per_launch, x):
+    """The chunk length of a sampler's launches and noise draws: iters_per_launch, refused below 1; None is
+    LSTMDecoderEngine.mh_default_iters_per_launch(T) for a 2-D tensor x (T = 33 for anything else)."""
+    if iters_per_launch is None:
+        T = x.size(1) if (torch.is_tensor(x) and x.dim() == 2) else 33
+        return LSTMDecoderEngine.mh_default_iters_per_launch(T)
+    per = int(iters_per_launch)
+    if per < 1:
+        raise ValueError("%s: iters_per_launch >= 1 expected" % who)
+    return per
+
+
+def _prefetch_noise(who, draw, total, per, B, C, nz, device, device_msg=None):
+    """Every chunk's noise of a fused chain, fetched and checked before the first launch -> [(i0, n, eps, u)], float32 and
+    contiguous.  device_msg: the caller's wording of the device refusal (filled with eps's, u's and x's device); None:
+    _same_device's."""
+    chunks = []
+    for i0 in range(0, total, per):
+        n = min(per, total - i0)
+        eps, u = draw(i0, n)
+        if device_msg is None:
+            _same_device(who, device, eps=eps, u=u)
+        elif eps.device != device or u.device != device:
+            raise _lib.LvaeError(device_msg % (eps.device, u.device, device))
+        if tuple(eps.shape) != (n, B, C, nz) or tuple(u.shape) != (n, B, C):
+            raise ValueError("%s: eps [%d][%d][%d][%d] and u [%d][%d][%d] expected, got %s and %s"
+                             % (who, n, B, C, nz, n, B, C, tuple(eps.shape), tuple(u.shape)))
+        chunks.append((i0, n, eps.contiguous().float(), u.contiguous().float()))
+    return chunks
+
+
 def _lstm_forward(eng, lib, s, img, w, Gx, whh, mask, scale, hdrop, T, B, H, device, steps=None, xin=None):
     """The forward recurrence of one LSTM layer: exact f32, bf16 launch-per-step, or (bf16 image path on a >= 256-CU
     device, H = 1024, B <= 128) the single persistent launch of lv_lstm_persist16.hip.  steps = (int32 [B] on the device,
@@ -1756,7 +1787,6 @@ class LSTMDecoderEngine(object):
             raise _lib.LvaeError("cond_ll: z is on %s, x on %s" % (z.device, device))
         self.ensure(device)
         V, ni, H, nz = self.dims()
-        v = self.flat.views
         B, T = x.shape
         if x.dtype != torch.int64 or z.dim() not in (2, 3) or z.shape[-1] != nz or (z.dim() == 3 and z.shape[0] != B):
             raise ValueError("cond_ll: x int64 [B][T] and z [K][%d] or [B][K][%d] expected, got %s %s and %s"
@@ -1767,11 +1797,24 @@ class LSTMDecoderEngine(object):
         z_stride = 0 if z.dim() == 2 else K * nz
         ws = torch.empty(self.lib.lv_dec_cond_ll_f32_ws_floats(V, H, nz, B, T), dtype=torch.float32, device=device)
         out = torch.empty(B, K, dtype=torch.float32, device=device)
-        self.lib.lv_dec_cond_ll_f32(P(x), B, T, P(z), z_stride, K, P(v["embed.weight"]), P(v["trans_linear.weight"]),
-                                    P(v["lstm.weight_ih_l0"]), P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]),
-                                    P(v["lstm.bias_hh_l0"]), P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), P(out),
+        self.lib.lv_dec_cond_ll_f32(P(x), B, T, P(z), z_stride, K, *self._weight_ptrs(), V, ni, H, nz, P(ws), P(out),
                                     stream_ptr(device))
         return out
+
+    def _weight_ptrs(self):
+        """The decoder's seven weight pointers, in the order lv_dec_cond_ll_f32 and lv_mh_chain_prep_f32 take them."""
+        v = self.flat.views
+        return [P(v[k]) for k in ("embed.weight", "trans_linear.weight", "lstm.weight_ih_l0", "lstm.weight_hh_l0",
+                                  "lstm.bias_ih_l0", "lstm.bias_hh_l0", "pred_linear.weight")]
+
+    def _chain_prep(self, x):
+        """The workspace of the fused chains (lv_mh_chain_f32, lv_ais_chain_f32) for the contiguous batch x, filled by
+        lv_mh_chain_prep_f32: the weight images and the per-sentence input projection, once per call."""
+        V, ni, H, nz = self.dims()
+        B, T = x.shape
+        ws = torch.empty(self.lib.lv_mh_chain_f32_ws_floats(V, H, nz, B, T), dtype=torch.float32, device=x.device)
+        self.lib.lv_mh_chain_prep_f32(P(x), B, T, *self._weight_ptrs(), V, ni, H, nz, P(ws), stream_ptr(x.device))
+        return ws
 
     @staticmethod
     def mh_default_iters_per_launch(T):
@@ -1802,33 +1845,17 @@ class LSTMDecoderEngine(object):
         B, T = x.shape
         C = z0.shape[1]
         total = burn_in + nsamples * thin
-        per = self.mh_default_iters_per_launch(T) if iters_per_launch is None else int(iters_per_launch)
-        if per < 1:
-            raise ValueError("mh_chain: iters_per_launch >= 1 expected")
-        # every chunk's noise is fetched (and checked) before the first launch
-        chunks = []
-        for i0 in range(0, total, per):
-            n = min(per, total - i0)
-            eps, u = draw(i0, n)
-            if eps.device != device or u.device != device:
-                raise _lib.LvaeError("mh_chain: noise is on %s / %s, x on %s" % (eps.device, u.device, device))
-            if tuple(eps.shape) != (n, B, C, nz) or tuple(u.shape) != (n, B, C):
-                raise ValueError("mh_chain: eps [%d][%d][%d][%d] and u [%d][%d][%d] expected, got %s and %s"
-                                 % (n, B, C, nz, n, B, C, tuple(eps.shape), tuple(u.shape)))
-            chunks.append((i0, n, eps.contiguous().float(), u.contiguous().float()))
+        per = iters_per_launch_for("mh_chain", iters_per_launch, x)
+        chunks = _prefetch_noise("mh_chain", draw, total, per, B, C, nz, device, "mh_chain: noise is on %s / %s, x on %s")
         x = x.contiguous()
-        v = self.flat.views
         s = stream_ptr(device)
         f32 = dict(dtype=torch.float32, device=device)
         i32 = dict(dtype=torch.int32, device=device)
-        ws = torch.empty(self.lib.lv_mh_chain_f32_ws_floats(V, H, nz, B, T), **f32)
         cur = z0.detach().float().contiguous().clone()
         cur_ll, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **i32)
         samples = torch.empty(B, nsamples, C, nz, **f32)
         ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32)
-        self.lib.lv_mh_chain_prep_f32(P(x), B, T, P(v["embed.weight"]), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]),
-                                      P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]),
-                                      P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), s)
+        ws = self._chain_prep(x)
         for i0, n, eps, u in chunks:
             self.lib.lv_mh_chain_f32(P(x), B, T, P(ws), V, H, nz, C, P(cur), P(cur_ll), P(accepts), P(eps), P(u), n, i0, burn_in,
                                      thin, nsamples, float(std), 1 if i0 == 0 else 0, P(samples), P(ratios, i0 * B * C),
@@ -1859,35 +1886,21 @@ class LSTMDecoderEngine(object):
             raise ValueError("ais_chain: beta float64 [N + 1] and std_it [N], N >= 1, expected")
         if (mu0 is None) != (lv0 is None) or (mu0 is not None and (tuple(mu0.shape) != (B, nz) or tuple(lv0.shape) != (B, nz))):
             raise ValueError("ais_chain: mu0 and lv0 [%d][%d] (or both None) expected" % (B, nz))
-        per = self.mh_default_iters_per_launch(T) if iters_per_launch is None else int(iters_per_launch)
-        if per < 1:
-            raise ValueError("ais_chain: iters_per_launch >= 1 expected")
-        chunks = []                                  # every chunk's noise is fetched (and checked) before the first launch
-        for i0 in range(0, total, per):
-            n = min(per, total - i0)
-            eps, u = draw(i0, n)
-            _same_device("ais_chain", device, eps=eps, u=u)
-            if tuple(eps.shape) != (n, B, C, nz) or tuple(u.shape) != (n, B, C):
-                raise ValueError("ais_chain: eps [%d][%d][%d][%d] and u [%d][%d][%d] expected, got %s and %s"
-                                 % (n, B, C, nz, n, B, C, tuple(eps.shape), tuple(u.shape)))
-            chunks.append((i0, n, eps.contiguous().float(), u.contiguous().float()))
+        per = iters_per_launch_for("ais_chain", iters_per_launch, x)
+        chunks = _prefetch_noise("ais_chain", draw, total, per, B, C, nz, device)
         x = x.contiguous()
         beta, std_it = beta.contiguous(), std_it.contiguous().float()
         if mu0 is not None:
             mu0, lv0 = mu0.detach().contiguous().float(), lv0.detach().contiguous().float()
-        v = self.flat.views
         s = stream_ptr(device)
         f32 = dict(dtype=torch.float32, device=device)
-        ws = torch.empty(self.lib.lv_mh_chain_f32_ws_floats(V, H, nz, B, T), **f32)
         cur = z0.detach().float().contiguous().clone()
         g, lq = torch.zeros(B, C, **f32), torch.zeros(B, C, **f32)
         logw = torch.zeros(B, C, dtype=torch.float64, device=device)
         accepts = torch.zeros(B, C, dtype=torch.int32, device=device)
         ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, dtype=torch.int32, device=device)
         trace = torch.empty(total, B, C, dtype=torch.float64, device=device)
-        self.lib.lv_mh_chain_prep_f32(P(x), B, T, P(v["embed.weight"]), P(v["trans_linear.weight"]), P(v["lstm.weight_ih_l0"]),
-                                      P(v["lstm.weight_hh_l0"]), P(v["lstm.bias_ih_l0"]), P(v["lstm.bias_hh_l0"]),
-                                      P(v["pred_linear.weight"]), V, ni, H, nz, P(ws), s)
+        ws = self._chain_prep(x)
         for i0, n, eps, u in chunks:
             self.lib.lv_ais_chain_f32(P(x), B, T, P(ws), V, H, nz, C, P(cur), P(g), P(lq), P(logw), P(accepts), P(eps), P(u),
                                       P(beta, i0), P(std_it, i0), P(mu0), P(lv0), n, 1 if i0 == 0 else 0, P(ratios, i0 * B * C),
@@ -2497,6 +2510,58 @@ def grid_posterior(cond_ll, z, want_log_post=True):
     return log_post, mean
 
 
+def _check_operands(who, anchor, device, ops, f64=(), i32=("accepts", "flag_out"), numel=None, cur_shape=None):
+    """The operands of one sampler launch (None: absent), each in turn: on `device` -- that of the operand named `anchor` -- then
+    contiguous and int32 (names in i32), float64 (in f64) or float32, then (numel given) numel(name) elements unless that is
+    None.  The kernels take raw pointers: the first operand that fails is refused before the launch."""
+    for name, t in ops.items():
+        if t is None:
+            continue
+        if t.device != device:
+            raise _lib.LvaeError("%s: %s is on %s, %s on %s" % (who, name, t.device, anchor, device))
+        want = torch.int32 if name in i32 else torch.float64 if name in f64 else torch.float32
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor" % (who, name, want))
+        n = None if numel is None else numel(name)
+        if n is not None and t.numel() != n:
+            raise ValueError("%s: %s has %d elements, %d expected for cur %s" % (who, name, t.numel(), n, cur_shape))
+
+
+def mh_keep_index(it, burn_in, thin, nsamples):
+    """Index of the kept sample that iteration `it` of a chain produces, or -1 (mh_keep_index of csrc/lv_cond_ll.h)."""
+    if it < burn_in or (it - burn_in) % thin != 0:
+        return -1
+    k = (it - burn_in) // thin
+    return k if k < nsamples else -1
+
+
+class NoiseCursor(object):
+    """The look-ahead over a per-iteration chain's noise, drawn in chunks of `per` iterations: the launch of iteration `it`
+    takes u[it] and the step noise (eps, momentum) of iteration it + 1.  draw(0, n) is asked for here, the next chunk when
+    it + 1 leaves the current one."""
+
+    def __init__(self, draw, total, per):
+        self.draw, self.total, self.per = draw, total, per
+        self._fetch(0)
+
+    def _fetch(self, c0):
+        self.c0 = c0                                              # first iteration of the chunk (noise, u) covers
+        self.noise, self.u = self.draw(c0, min(self.per, self.total - c0))
+
+    def first(self):
+        """The step noise of iteration 0, for the launch that scores the starting point."""
+        return self.noise[0]
+
+    def step(self, it):
+        """-> (u[it], the step noise of iteration it + 1 or None after the last)."""
+        u_it = self.u[it - self.c0]
+        if it + 1 >= self.total:
+            return u_it, None
+        if it + 1 - self.c0 >= self.noise.shape[0]:
+            self._fetch(it + 1)
+        return u_it, self.noise[it + 1 - self.c0]
+
+
 def mh_step(cond_ll, prop, cur, cur_ll, accepts, u, eps_next, std, samples, keep, init=False, ratio_out=None, flag_out=None):
     """One launch of lv_mh_step_f32, the propose / accept glue of VAE.sample_from_posterior (reference vae.py:218-254) for any
     decoder: cond_ll [B][C] = log p(x|prop) as eval_cond_ll returned it; prop, cur [B][C][nz], cur_ll [B][C] f32 and accepts
@@ -2505,16 +2570,9 @@ def mh_step(cond_ll, prop, cur, cur_ll, accepts, u, eps_next, std, samples, keep
     starting point, zero the counts, write the first proposals.  Every operand on one device, contiguous, or it is refused
     before the launch."""
     device = cond_ll.device
-    ops = {"prop": prop, "cur": cur, "cur_ll": cur_ll, "accepts": accepts, "u": u, "eps_next": eps_next, "samples": samples,
-           "ratio_out": ratio_out, "flag_out": flag_out}
-    for name, t in ops.items():
-        if t is None:
-            continue
-        if t.device != device:
-            raise _lib.LvaeError("mh_step: %s is on %s, cond_ll on %s" % (name, t.device, device))
-        want = torch.int32 if name in ("accepts", "flag_out") else torch.float32
-        if t.dtype != want or not t.is_contiguous():
-            raise ValueError("mh_step: %s must be a contiguous %s tensor" % (name, want))
+    _check_operands("mh_step", "cond_ll", device, {"prop": prop, "cur": cur, "cur_ll": cur_ll, "accepts": accepts, "u": u,
+                                                   "eps_next": eps_next, "samples": samples, "ratio_out": ratio_out,
+                                                   "flag_out": flag_out})
     lib, s = backend_for(device), stream_ptr(device)
     B, C, nz = cur.shape
     rows = B * C
@@ -2541,15 +2599,7 @@ def ais_step(cond_ll, prop, cur, g_cur, lq_cur, logw, accepts, u, beta, eps_next
     ops = {"prop": prop, "cur": cur, "g_cur": g_cur, "lq_cur": lq_cur, "logw": logw, "accepts": accepts, "u": u,
            "eps_next": eps_next, "mu0": mu0, "lv0": lv0, "ratio_out": ratio_out, "flag_out": flag_out,
            "logw_out_next": logw_out_next}
-    for name, t in ops.items():
-        if t is None:
-            continue
-        if t.device != device:
-            raise _lib.LvaeError("ais_step: %s is on %s, cond_ll on %s" % (name, t.device, device))
-        want = (torch.int32 if name in ("accepts", "flag_out") else torch.float64 if name in ("logw", "logw_out_next")
-                else torch.float32)
-        if t.dtype != want or not t.is_contiguous():
-            raise ValueError("ais_step: %s must be a contiguous %s tensor" % (name, want))
+    _check_operands("ais_step", "cond_ll", device, ops, f64=("logw", "logw_out_next"))
     lib, s = backend_for(device), stream_ptr(device)
     B, C, nz = cur.shape
     rows = B * C
@@ -2581,18 +2631,9 @@ def hmc_leap(rec, dz, st, mode, L, u=None, mom_next=None, beta=0.0, beta_next=0.
     rows = B * C
     ops = dict(st, rec=rec, dz=dz, u=u, mom_next=mom_next, mu0=mu0, lv0=lv0, dh_out=dh_out, flag_out=flag_out,
                logw_out_next=logw_out_next, keep_out=keep_out)
-    for name, t in ops.items():
-        if t is None:
-            continue
-        if t.device != device:
-            raise _lib.LvaeError("hmc_leap: %s is on %s, cur on %s" % (name, t.device, device))
-        want = (torch.int32 if name in ("accepts", "flag_out") else torch.float64 if name in ("logw", "logw_out_next")
-                else torch.float32)
-        if t.dtype != want or not t.is_contiguous():
-            raise ValueError("hmc_leap: %s must be a contiguous %s tensor" % (name, want))
-        n = rows * nz if name in ("pos", "mom", "cur", "d_cur", "mom_next", "keep_out") else B * nz if name in ("mu0", "lv0") else rows
-        if name != "dz" and t.numel() != n:
-            raise ValueError("hmc_leap: %s has %d elements, %d expected for cur %s" % (name, t.numel(), n, tuple(cur.shape)))
+    numel = lambda name: (None if name == "dz" else rows * nz if name in ("pos", "mom", "cur", "d_cur", "mom_next", "keep_out")
+                          else B * nz if name in ("mu0", "lv0") else rows)
+    _check_operands("hmc_leap", "cur", device, ops, f64=("logw", "logw_out_next"), numel=numel, cur_shape=tuple(cur.shape))
     if dz.numel() == 0 or dz.numel() % (rows * nz) != 0 or (mu0 is None) != (lv0 is None) or (mode == HMC_LAST and u is None):
         raise ValueError("hmc_leap: operand shapes do not match cur %s" % (tuple(cur.shape),))
     lib, s = backend_for(device), stream_ptr(device)
@@ -2636,29 +2677,23 @@ def hmc_chain(score, pos, draw, beta, L, step_size, adapt, mu0, lv0, keep=None, 
         tuned = dict(up=adapt[0], down=adapt[1], eps_min=adapt[2], eps_max=adapt[3])
         until = N if len(adapt) < 5 else int(adapt[4])
 
-    def chunk(c0):
-        m, u = draw(c0, min(per, N - c0))
+    def chunk(c0, n):
+        m, u = draw(c0, n)
         _same_device("hmc_chain", dev, mom=m, u=u)
         return m.float().contiguous(), u.float().contiguous()
-    mom, u = chunk(0)
-    c0 = 0                                                        # first transition of the chunk (mom, u) covers
+    noise = NoiseCursor(chunk, N, per)
     rec, dz, _ = score()
-    hmc_leap(rec, dz, st, HMC_INIT, L, mom_next=mom[0], beta_next=beta[1], dbeta_next=beta[1] - beta[0], mu0=mu0, lv0=lv0,
+    hmc_leap(rec, dz, st, HMC_INIT, L, mom_next=noise.first(), beta_next=beta[1], dbeta_next=beta[1] - beta[0], mu0=mu0, lv0=lv0,
              logw_out_next=trace[0])
     for it in range(N):                                           # transition it + 1 of the contract, at beta[it + 1]
         for _ in range(L - 1):
             rec, dz, _ = score()
             hmc_leap(rec, dz, st, HMC_MID, L, beta=beta[it + 1], mu0=mu0, lv0=lv0)
         rec, dz, _ = score()
-        u_it = u[it - c0]
+        u_it, mom_next = noise.step(it)
         more = it + 1 < N
-        if more and it + 1 - c0 >= mom.shape[0]:
-            c0 = it + 1
-            mom, u = chunk(c0)
-        k = -1
-        if keep is not None and it >= burn_in and (it - burn_in) % thin == 0 and (it - burn_in) // thin < nsamples:
-            k = (it - burn_in) // thin
-        hmc_leap(rec, dz, st, HMC_LAST, L, u=u_it, mom_next=mom[it + 1 - c0] if more else None, beta=beta[it + 1],
+        k = -1 if keep is None else mh_keep_index(it, burn_in, thin, nsamples)
+        hmc_leap(rec, dz, st, HMC_LAST, L, u=u_it, mom_next=mom_next, beta=beta[it + 1],
                  beta_next=beta[it + 2] if more else 0.0, dbeta_next=beta[it + 2] - beta[it + 1] if more else 0.0, mu0=mu0, lv0=lv0,
                  dh_out=ratios[it], flag_out=flags[it], logw_out_next=trace[it + 1] if more else None,
                  keep_out=kept[k] if k >= 0 else None, **(tuned if it < until else fixed))

@@ -479,26 +479,35 @@ class VAE(nn.Module):
     # False forces the generic route below (A/B runs, tests)
     fused_grid = True
 
-    def _fused_grid_ok(self, x, grid_z):
-        """The fused grid kernels compute the eval-mode decoder without autograd: usable when no dropout mask would be drawn
-        (the decoder is not training, or both its dropout p are 0), autograd is off (every call site in toy.py runs under
-        torch.no_grad(); with grad enabled the generic route keeps the result differentiable), x and the grid share one
-        device, and an LSTM decoder is inside lv_dec_cond_ll_f32's envelope on a device the package has kernels for.
-        Anything else keeps the generic route and its behaviour, errors included (e.g. toy.py's epoch-end dump, which runs in
-        train mode and draws dropout masks there)."""
+    def _fused_decoder(self, switch, x, same_device=(), needs_no_dropout=False):
+        """What every fused evaluation route asks first -> the decoder's engine, or None where the route is closed: its class
+        switch is on, the decoder is an LSTM decoder, x is a 2-D int64 tensor, the tensors of same_device live on x's device,
+        (needs_no_dropout: the kernel computes the eval-mode decoder) no dropout mask would be drawn -- the decoder is not
+        training, or both its dropout p are 0 -- and x's device is one the package has kernels for.  The caller adds its own
+        conditions and asks the engine for its kernel's envelope."""
         dec = self.decoder
         eng = getattr(dec, "_hip", None)
-        if not (self.fused_grid and not torch.is_grad_enabled() and isinstance(eng, _eng.LSTMDecoderEngine)
-                and torch.is_tensor(x) and x.dim() == 2 and x.dtype == torch.int64 and torch.is_tensor(grid_z)
-                and grid_z.device == x.device and grid_z.dim() == 2 and grid_z.size(1) == self.nz):
-            return False
-        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
-            return False
+        if not (switch and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
+                and x.dtype == torch.int64 and all(t.device == x.device for t in same_device)):
+            return None
+        if needs_no_dropout and dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
+            return None
         try:
             eng.ensure(x.device)
         except _lib.LvaeError:
+            return None
+        return eng
+
+    def _fused_grid_ok(self, x, grid_z):
+        """The fused grid kernels compute the eval-mode decoder without autograd: usable where _fused_decoder allows it (no
+        dropout mask would be drawn; x and the grid share one device), autograd is off (every call site in toy.py runs under
+        torch.no_grad(); with grad enabled the generic route keeps the result differentiable), the grid is (K, nz), and the
+        decoder is inside lv_dec_cond_ll_f32's envelope.  Anything else keeps the generic route and its behaviour, errors
+        included (e.g. toy.py's epoch-end dump, which runs in train mode and draws dropout masks there)."""
+        if torch.is_grad_enabled() or not (torch.is_tensor(grid_z) and grid_z.dim() == 2 and grid_z.size(1) == self.nz):
             return False
-        return eng.cond_ll_supported(x.size(1))
+        eng = self._fused_decoder(self.fused_grid, x, (grid_z,), needs_no_dropout=True)
+        return eng is not None and eng.cond_ll_supported(x.size(1))
 
     def _fused_grid_posterior(self, x, grid_z, want_log_post):
         cond = self.decoder._hip.cond_ll(x, grid_z)
@@ -527,21 +536,59 @@ class VAE(nn.Module):
     fused_mh = True
 
     def _fused_mh_ok(self, x, z0):
-        """Route "chain" of sample_from_posterior, in the spirit of _fused_grid_ok: an LSTM decoder inside lv_mh_chain_f32's
-        envelope that draws no dropout mask (not training, or both p are 0), x a 2-D int64 tensor, everything on one device
-        the package has kernels for."""
-        dec = self.decoder
-        eng = getattr(dec, "_hip", None)
-        if not (self.fused_mh and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
-                and x.dtype == torch.int64 and z0.device == x.device):
-            return False
-        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
-            return False
-        try:
-            eng.ensure(x.device)
-        except _lib.LvaeError:
-            return False
-        return eng.cond_ll_supported(x.size(1))
+        """Route "chain" of sample_from_posterior: _fused_decoder's conditions (no dropout mask drawn, z0 on x's device) and
+        lv_mh_chain_f32's envelope."""
+        eng = self._fused_decoder(self.fused_mh, x, (z0,), needs_no_dropout=True)
+        return eng is not None and eng.cond_ll_supported(x.size(1))
+
+    def _chain_noise(self, who, x, chains, total, noise, generator, name="eps", iterations_only=False):
+        """The random draws of `total` chain iterations -> (z0 or None, draw).  noise = (z0 [B][chains][nz], the step noise `name`
+        [total][B][chains][nz], u [total][B][chains]) is checked -- the device first: the kernels take raw pointers, so a
+        mismatch is refused before anything is launched; iterations_only: of the shapes only the two iteration counts -- and
+        draw(i0, n) hands out its slices as contiguous float32.  noise None: z0 is left to _chain_start, and draw(i0, n) is one
+        torch.randn and one torch.rand on x's device (`generator` optional)."""
+        dev = x.device if torch.is_tensor(x) else x[0].device
+        B = x.size(0) if torch.is_tensor(x) else x[0].size(0)
+        nz = self.nz
+        z0 = step_all = u_all = None
+        if noise is not None:
+            z0, step_all, u_all = noise
+            for nm, t in (("z0", z0), (name, step_all), ("u", u_all)):
+                if t.device != dev:
+                    raise _lib.LvaeError("%s: %s is on %s, x on %s" % (who, nm, t.device, dev))
+            if iterations_only:
+                if step_all.shape[0] != total or u_all.shape[0] != total:
+                    raise ValueError("%s: noise for %d iterations expected" % (who, total))
+            elif (tuple(z0.shape) != (B, chains, nz) or tuple(step_all.shape) != (total, B, chains, nz)
+                    or tuple(u_all.shape) != (total, B, chains)):
+                raise ValueError("%s: noise z0 [%d][%d][%d], %s [%d][%d][%d][%d], u [%d][%d][%d] expected, got %s, %s, %s"
+                                 % (who, B, chains, nz, name, total, B, chains, nz, total, B, chains, tuple(z0.shape),
+                                    tuple(step_all.shape), tuple(u_all.shape)))
+
+        def draw(i0, n):
+            if noise is None:
+                return (torch.randn(n, B, chains, nz, device=dev, generator=generator),
+                        torch.rand(n, B, chains, device=dev, generator=generator))
+            return step_all[i0:i0 + n].float().contiguous(), u_all[i0:i0 + n].float().contiguous()
+        return z0, draw
+
+    def _chain_start(self, x, chains, init, z0, generator):
+        """Where the chains start -> (z0 [B][chains][nz], mu0, lv0), contiguous float32; mu0 / lv0 [B][nz] are q0's statistics
+        for init "encoder", None (q0 = the prior) otherwise.  z0 None: drawn from q(z|x) by encoder.sample (init "encoder", and
+        "sampler": sample_from_posterior's start) or from the prior by torch.randn on x's device (`generator` optional)."""
+        mu0 = lv0 = None
+        if init == "encoder":
+            if z0 is None:
+                z0, (mu0, lv0) = self.encoder.sample(x, chains)
+            else:
+                mu0, lv0 = self.encode_stats(x)
+            mu0, lv0 = mu0.detach().float().contiguous(), lv0.detach().float().contiguous()
+        elif z0 is None and init == "sampler":
+            z0 = self.encoder.sample(x, chains)[0]
+        elif z0 is None:
+            xb = x if torch.is_tensor(x) else x[0]
+            z0 = torch.randn(xb.size(0), chains, self.nz, device=xb.device, generator=generator)
+        return z0.detach().float().contiguous(), mu0, lv0
 
     def sample_from_posterior(self, x, nsamples, chains=1, burn_in=None, thin=None, std=None, noise=None, generator=None,
                               iters_per_launch=None, return_info=False, transition="rw", leapfrog=10, step_size=None, adapt=None,
@@ -612,28 +659,11 @@ class VAE(nn.Module):
         std = float(vals[2])
         x = self._batch(x)
         with torch.no_grad():
-            dev = x.device if torch.is_tensor(x) else x[0].device
-            if noise is not None:
-                z0, eps_all, u_all = noise
-                for name, t in (("z0", z0), ("eps", eps_all), ("u", u_all)):
-                    if t.device != dev:          # the kernels take raw pointers: refused before anything is launched
-                        raise _lib.LvaeError("sample_from_posterior: %s is on %s, x on %s" % (name, t.device, dev))
-                if eps_all.shape[0] != total or u_all.shape[0] != total:
-                    raise ValueError("sample_from_posterior: noise for %d iterations expected" % total)
-            else:
-                z0 = self.encoder.sample(x, chains)[0]
-                eps_all = u_all = None
-            z0 = z0.detach().float().contiguous()
-            B, C, nz = z0.shape
+            z0, draw = self._chain_noise("sample_from_posterior", x, chains, total, noise, generator, iterations_only=True)
+            z0 = self._chain_start(x, chains, "sampler", z0, generator)[0]
+            _, C, nz = z0.shape
             if C != chains or nz != self.nz:
                 raise ValueError("sample_from_posterior: z0 [B][%d][%d] expected, got %s" % (chains, self.nz, tuple(z0.shape)))
-
-            def draw(i0, n):
-                if eps_all is not None:
-                    return eps_all[i0:i0 + n].float().contiguous(), u_all[i0:i0 + n].float().contiguous()
-                return (torch.randn(n, B, C, nz, device=dev, generator=generator),
-                        torch.rand(n, B, C, device=dev, generator=generator))
-
             if self._fused_mh_ok(x, z0):
                 route = "chain"
                 r = self.decoder._hip.mh_chain(x, z0, draw, burn_in, thin, nsamples, std, iters_per_launch)
@@ -652,30 +682,19 @@ class VAE(nn.Module):
         dev = z0.device
         B, C, nz = z0.shape
         total = burn_in + nsamples * thin
-        if iters_per_launch is None:
-            T = x.size(1) if (torch.is_tensor(x) and x.dim() == 2) else 33
-            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
-        per = int(iters_per_launch)
-        if per < 1:
-            raise ValueError("sample_from_posterior: iters_per_launch >= 1 expected")
+        per = _eng.iters_per_launch_for("sample_from_posterior", iters_per_launch, x)
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         cur, prop = z0.clone(), z0.clone()
         cur_ll, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **i32)
         samples = torch.empty(B, nsamples, C, nz, **f32)
         ratios, flags = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32)
-        eps, u = draw(0, min(per, total))
-        c0 = 0                                                    # first iteration of the chunk (eps, u) covers
-        _eng.mh_step(self.eval_cond_ll(x, cur), prop, cur, cur_ll, accepts, None, eps[0], std, samples, -1, init=True)
+        noise = _eng.NoiseCursor(draw, total, per)
+        _eng.mh_step(self.eval_cond_ll(x, cur), prop, cur, cur_ll, accepts, None, noise.first(), std, samples, -1, init=True)
         for it in range(total):
             cond = self.eval_cond_ll(x, prop)
-            u_it = u[it - c0]
-            if it + 1 < total and it + 1 - c0 >= eps.shape[0]:
-                c0 = it + 1
-                eps, u = draw(c0, min(per, total - c0))
-            eps_next = eps[it + 1 - c0] if it + 1 < total else None
-            keep = (it - burn_in) // thin if (it >= burn_in and (it - burn_in) % thin == 0) else -1
-            _eng.mh_step(cond, prop, cur, cur_ll, accepts, u_it, eps_next, std, samples, keep, ratio_out=ratios[it],
-                         flag_out=flags[it])
+            u_it, eps_next = noise.step(it)
+            _eng.mh_step(cond, prop, cur, cur_ll, accepts, u_it, eps_next, std, samples,
+                         _eng.mh_keep_index(it, burn_in, thin, nsamples), ratio_out=ratios[it], flag_out=flags[it])
         return samples, cur_ll, accepts, ratios, flags
 
     # True: nll_ais takes the fused chain kernel (lv_ais_chain_f32) where _fused_ais_ok allows it; False forces the
@@ -683,19 +702,9 @@ class VAE(nn.Module):
     fused_ais = True
 
     def _fused_ais_ok(self, x, z0):
-        """Route "chain" of nll_ais: the conditions of _fused_mh_ok with the AIS kernel's own envelope."""
-        dec = self.decoder
-        eng = getattr(dec, "_hip", None)
-        if not (self.fused_ais and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
-                and x.dtype == torch.int64 and z0.device == x.device):
-            return False
-        if dec.training and (dec.dropout_in.p > 0 or dec.dropout_out.p > 0):
-            return False
-        try:
-            eng.ensure(x.device)
-        except _lib.LvaeError:
-            return False
-        return eng.ais_chain_supported(x.size(1))
+        """Route "chain" of nll_ais: _fused_decoder's conditions, as _fused_mh_ok asks for them, and lv_ais_chain_f32's envelope."""
+        eng = self._fused_decoder(self.fused_ais, x, (z0,), needs_no_dropout=True)
+        return eng is not None and eng.ais_chain_supported(x.size(1))
 
     @staticmethod
     def ais_schedule(schedule, temps, transitions=1):
@@ -794,37 +803,8 @@ class VAE(nn.Module):
         x = self._batch(x)
         with torch.no_grad():
             dev = x.device if torch.is_tensor(x) else x[0].device
-            B = x.size(0) if torch.is_tensor(x) else x[0].size(0)
-            nz = self.nz
-            if noise is not None:
-                z0, eps_all, u_all = noise
-                for name, t in (("z0", z0), ("eps", eps_all), ("u", u_all)):
-                    if t.device != dev:          # the kernels take raw pointers: refused before anything is launched
-                        raise _lib.LvaeError("nll_ais: %s is on %s, x on %s" % (name, t.device, dev))
-                if (tuple(z0.shape) != (B, chains, nz) or tuple(eps_all.shape) != (total, B, chains, nz)
-                        or tuple(u_all.shape) != (total, B, chains)):
-                    raise ValueError("nll_ais: noise z0 [%d][%d][%d], eps [%d][%d][%d][%d], u [%d][%d][%d] expected, got %s, %s, %s"
-                                     % (B, chains, nz, total, B, chains, nz, total, B, chains, tuple(z0.shape),
-                                        tuple(eps_all.shape), tuple(u_all.shape)))
-            mu0 = lv0 = None
-            if init == "encoder":
-                if noise is None:
-                    z0, (mu0, lv0) = self.encoder.sample(x, chains)
-                else:
-                    mu0, lv0 = self.encode_stats(x)
-                mu0, lv0 = mu0.detach().float().contiguous(), lv0.detach().float().contiguous()
-            elif noise is None:
-                z0 = torch.randn(B, chains, nz, device=dev, generator=generator)
-            if noise is None:
-                eps_all = u_all = None
-            z0 = z0.detach().float().contiguous()
-
-            def draw(i0, n):
-                if eps_all is not None:
-                    return eps_all[i0:i0 + n].float().contiguous(), u_all[i0:i0 + n].float().contiguous()
-                return (torch.randn(n, B, chains, nz, device=dev, generator=generator),
-                        torch.rand(n, B, chains, device=dev, generator=generator))
-
+            z0, draw = self._chain_noise("nll_ais", x, chains, total, noise, generator)
+            z0, mu0, lv0 = self._chain_start(x, chains, init, z0, generator)
             if self._fused_ais_ok(x, z0):
                 route = "chain"
                 r = self.decoder._hip.ais_chain(x, z0, draw, torch.tensor(beta, dtype=torch.float64, device=dev),
@@ -857,36 +837,27 @@ class VAE(nn.Module):
         dev = z0.device
         B, C, nz = z0.shape
         total = len(stds)
-        if iters_per_launch is None:
-            T = x.size(1) if (torch.is_tensor(x) and x.dim() == 2) else 33
-            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
-        per = int(iters_per_launch)
-        if per < 1:
-            raise ValueError("nll_ais: iters_per_launch >= 1 expected")
+        per = _eng.iters_per_launch_for("nll_ais", iters_per_launch, x)
         f32, i32, f64 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.float64))
         cur, prop = z0.clone(), z0.clone()
         g, lq, logw, accepts = torch.zeros(B, C, **f32), torch.zeros(B, C, **f32), torch.zeros(B, C, **f64), torch.zeros(B, C, **i32)
         ratios, flags, trace = torch.empty(total, B, C, **f32), torch.empty(total, B, C, **i32), torch.empty(total, B, C, **f64)
-        eps, u = draw(0, min(per, total))
-        c0 = 0                                                    # first iteration of the chunk (eps, u) covers
+        noise = _eng.NoiseCursor(draw, total, per)
         try:
             cond0 = self.eval_cond_ll(x, cur)
         except (TypeError, AttributeError) as e:
             if torch.is_tensor(x):
                 raise
             raise ValueError("nll_ais: this decoder's eval_cond_ll does not take a variable-length pair (%s)" % e)
-        _eng.ais_step(cond0, prop, cur, g, lq, logw, accepts, None, 0.0, eps[0], stds[0], beta[1] - beta[0],
+        _eng.ais_step(cond0, prop, cur, g, lq, logw, accepts, None, 0.0, noise.first(), stds[0], beta[1] - beta[0],
                       mu0, lv0, init=True, logw_out_next=trace[0])
         for it in range(total):                                   # iteration it + 1 of the contract, at beta[it + 1]
             cond = self.eval_cond_ll(x, prop)
-            u_it = u[it - c0]
+            u_it, eps_next = noise.step(it)
             more = it + 1 < total
-            if more and it + 1 - c0 >= eps.shape[0]:
-                c0 = it + 1
-                eps, u = draw(c0, min(per, total - c0))
-            _eng.ais_step(cond, prop, cur, g, lq, logw, accepts, u_it, beta[it + 1], eps[it + 1 - c0] if more else None,
-                          stds[it + 1] if more else 0.0, beta[it + 2] - beta[it + 1] if more else 0.0, mu0, lv0,
-                          ratio_out=ratios[it], flag_out=flags[it], logw_out_next=trace[it + 1] if more else None)
+            _eng.ais_step(cond, prop, cur, g, lq, logw, accepts, u_it, beta[it + 1], eps_next, stds[it + 1] if more else 0.0,
+                          beta[it + 2] - beta[it + 1] if more else 0.0, mu0, lv0, ratio_out=ratios[it], flag_out=flags[it],
+                          logw_out_next=trace[it + 1] if more else None)
         return {"logw": logw, "cur": cur, "g": g, "accepts": accepts, "ratios": ratios, "flags": flags, "logw_trace": trace}
 
     # True: transition="hmc" takes the decoder engine's session (LSTMDecoderEngine.hmc_ais) where _fused_hmc_ok allows it; False
@@ -894,17 +865,10 @@ class VAE(nn.Module):
     fused_hmc = True
 
     def _fused_hmc_ok(self, x, B, C):
-        """Route "hmc-fused", in the style of _fused_svi_ok: an LSTM decoder, x a 2-D int64 tensor on a device the package has
-        kernels for, B * C decoder rows inside the session's envelope."""
-        eng = getattr(self.decoder, "_hip", None)
-        if not (self.fused_hmc and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
-                and x.dtype == torch.int64):
-            return False
-        try:
-            eng.ensure(x.device)
-        except _lib.LvaeError:
-            return False
-        return eng.svi_supported(B, C)
+        """Route "hmc-fused": _fused_decoder's conditions (the session runs in eval arithmetic: dropout does not matter), B * C
+        decoder rows inside the session's envelope."""
+        eng = self._fused_decoder(self.fused_hmc, x)
+        return eng is not None and eng.svi_supported(B, C)
 
     def _hmc_arguments(self, who, field, leapfrog, step_size, adapt, step_bounds):
         """-> (L, step_size, None or (up, down, eps_min, eps_max)) or ValueError; up / down are rounded to float32 here, as the
@@ -934,43 +898,16 @@ class VAE(nn.Module):
         decoder runs in eval arithmetic and the training flags are restored."""
         if isinstance(x, (tuple, list)):
             raise ValueError("%s: transition='hmc' does not take variable-length batches (x, lengths); batch by length" % who)
-        if iters_per_launch is not None and int(iters_per_launch) < 1:
-            raise ValueError("%s: iters_per_launch >= 1 expected" % who)
-        B, dev, nz, total = x.size(0), x.device, self.nz, len(beta) - 1
-        if noise is not None:
-            z0, mom_all, u_all = noise
-            for name, t in (("z0", z0), ("mom", mom_all), ("u", u_all)):
-                if t.device != dev:              # the kernels take raw pointers: refused before anything is launched
-                    raise _lib.LvaeError("%s: %s is on %s, x on %s" % (who, name, t.device, dev))
-            if (tuple(z0.shape) != (B, chains, nz) or tuple(mom_all.shape) != (total, B, chains, nz)
-                    or tuple(u_all.shape) != (total, B, chains)):
-                raise ValueError("%s: noise z0 [%d][%d][%d], mom [%d][%d][%d][%d], u [%d][%d][%d] expected, got %s, %s, %s"
-                                 % (who, B, chains, nz, total, B, chains, nz, total, B, chains, tuple(z0.shape),
-                                    tuple(mom_all.shape), tuple(u_all.shape)))
+        per = _eng.iters_per_launch_for(who, iters_per_launch, x)
+        z0, draw = self._chain_noise(who, x, chains, len(beta) - 1, noise, generator, name="mom")
         flags = [(m, m.training) for m in self.modules()]
         try:
             self.eval()
             with torch.no_grad():
-                mu0 = lv0 = None
-                if init == "encoder":
-                    if noise is None:
-                        z0, (mu0, lv0) = self.encoder.sample(x, chains)
-                    else:
-                        mu0, lv0 = self.encode_stats(x)
-                    mu0, lv0 = mu0.detach().float().contiguous(), lv0.detach().float().contiguous()
-                elif noise is None:
-                    z0 = (self.encoder.sample(x, chains)[0] if init == "sampler"
-                          else torch.randn(B, chains, nz, device=dev, generator=generator))
-                z0 = z0.detach().float().contiguous()
-
-                def draw(i0, n):
-                    if noise is not None:
-                        return mom_all[i0:i0 + n], u_all[i0:i0 + n]
-                    return (torch.randn(n, B, chains, nz, device=dev, generator=generator),
-                            torch.rand(n, B, chains, device=dev, generator=generator))
-                if self._fused_hmc_ok(x, B, chains):
-                    return self.decoder._hip.hmc_ais(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch), "hmc-fused"
-                return self._hmc_generic(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch), "hmc-generic"
+                z0, mu0, lv0 = self._chain_start(x, chains, init, z0, generator)
+                if self._fused_hmc_ok(x, x.size(0), chains):
+                    return self.decoder._hip.hmc_ais(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, per), "hmc-fused"
+                return self._hmc_generic(x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, per), "hmc-generic"
         finally:
             for m, t in flags:
                 m.training = t
@@ -978,9 +915,6 @@ class VAE(nn.Module):
     def _hmc_generic(self, x, z0, draw, beta, L, step_size, adapt, mu0, lv0, keep, iters_per_launch):
         """Route "hmc-generic": rec and d rec / d z from what every decoder has -- reconstruct_error and its autograd backward, as
         _svi_generic gets them -- and lv_hmc_leap_f32 (one plain gradient: parts = 1) for everything else."""
-        if iters_per_launch is None:
-            T = x.size(1) if x.dim() == 2 else 33
-            iters_per_launch = _eng.LSTMDecoderEngine.mh_default_iters_per_launch(T)
         pos = z0.clone()
 
         def score():
@@ -1018,17 +952,10 @@ class VAE(nn.Module):
     fused_svi = True
 
     def _fused_svi_ok(self, x, B, ns):
-        """Route "fused" of refine_posterior, in the style of _fused_mh_ok: an LSTM decoder, x a 2-D int64 tensor on a device the
-        package has kernels for, B * ns decoder rows inside the LDS budget of the decoder's batch-sized ends."""
-        eng = getattr(self.decoder, "_hip", None)
-        if not (self.fused_svi and isinstance(eng, _eng.LSTMDecoderEngine) and torch.is_tensor(x) and x.dim() == 2
-                and x.dtype == torch.int64):
-            return False
-        try:
-            eng.ensure(x.device)
-        except _lib.LvaeError:
-            return False
-        return eng.svi_supported(B, ns)
+        """Route "fused" of refine_posterior: _fused_decoder's conditions (the refinement runs in eval arithmetic: dropout does not
+        matter), B * ns decoder rows inside the LDS budget of the decoder's batch-sized ends."""
+        eng = self._fused_decoder(self.fused_svi, x)
+        return eng is not None and eng.svi_supported(B, ns)
 
     def refine_posterior(self, x, steps=20, lr=1.0, momentum=0.5, clip=5.0, kl_weight=1.0, nsamples=1, noise=None, generator=None,
                          keep="best", return_info=False):
